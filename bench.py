@@ -24,8 +24,15 @@ One step = ONE kernel launch of hmc_random_iters that advances every chain of th
 row stored).  The timed launches store every q_chain row, E and dE (the reference's output
 contract, samplers.py:436-471) into a circular device window of the last R rows (R <= K*S, sized to
 --chain-budget-gb; 1M chains x 100 dims is 0.8 GB per row).  After the timed region the window
-holds the last R samples of every chain; R-hat / ESS (reference estimator, utils.py:77-179) run on
-them, and ESS/s = n_eff(R samples) / (time the timed loop spent producing R iterations).
+holds the last R samples of every chain.
+
+A plain run sets up, warms up, times the K steps and prints the result line (value = leapfrog
+steps/s, ms_per_step = one timed step).  --full adds what takes work of its own: R-hat / ESS
+(reference estimator, utils.py:77-179) on the window's R samples, with ESS/s = n_eff(R samples) /
+(time the timed loop spent producing R iterations); the CPU baseline; board power and shader clock
+sampled during the timed steps.  (--stream-diag feeds its statistics inside the timed steps, so its
+R-hat / ESS are reported by every run.)  --dump-outputs DIR writes the last timed step's outputs
+for a seeded sample of chains as DIR/<name>.npy, so that two builds can be compared.
 """
 import argparse
 import json
@@ -100,7 +107,14 @@ def parse(argv=None):
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process group of N > 1 runs: nccl (= RCCL over xGMI, one GPU per rank) or gloo "
                          "(host-side collectives; lets a test run several ranks on one GPU)")
-    ap.add_argument("--no-telemetry", action="store_true", help="do not sample board power / shader clock")
+    ap.add_argument("--no-telemetry", action="store_true",
+                    help="--full: do not sample board power / shader clock")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the CPU baseline, R-hat / ESS of the q_chain "
+                         "window after the timed steps, board power / shader clock during them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float64; "
+                         "a fixed, seeded sample of the chains, well under 64 MB in all)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / sharding check without a GPU: every rank joins a gloo group and reports "
                          "its global chain range; rank 0 prints them as one JSON line")
@@ -306,6 +320,39 @@ class Telemetry:
                     error=self.error)
 
 
+DUMP_SEED = 20240607         # the dumped chains are the same for every run of the same arguments
+DUMP_ROW_BYTES = 32 << 20    # budget of the q_chain rows, by far the largest dumped array
+
+
+def dump_outputs(path, eng, window, K, S, offset, diag=None):
+    """--dump-outputs: what the last timed step left for a caller of the timed path, for a seeded
+    sample of this rank's chains, as float64 .npy files:
+        chains    global ids of the sampled chains
+        q_rows    the q_chain rows the step stored (its last min(S, window rows) iterations, oldest first)
+        E, dE     E_chain / dE_chain of the step's S iterations
+        q, E_prev chain state after the step
+        rhat, n_eff  (--stream-diag) the statistics the timed steps fed, over all chains"""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    N, D = eng.N, eng.D
+    rows = min(S, window.shape[1]) if window is not None else 0
+    n_s = min(N, max(1, DUMP_ROW_BYTES // (8 * D * max(rows, 1))))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(N, size=n_s, replace=False))
+    idx_t = torch.as_tensor(idx, dtype=torch.int64, device=eng.device)
+    out = {"chains": (idx + offset).astype(np.float64), "q": eng.q[idx_t], "E_prev": eng.E_prev[idx_t]}
+    if eng.E_chain is not None:         # chain rows (K-1)*S .. K*S-1 are the last step's iterations
+        out["E"] = eng.E_chain[idx_t, (K - 1) * S:K * S]
+        out["dE"] = eng.dE_chain[idx_t, (K - 1) * S:K * S]
+    if rows:                            # chain row r sits at window row r % (window rows)
+        slots = torch.arange(K * S - rows, K * S, dtype=torch.int64, device=eng.device) % window.shape[1]
+        out["q_rows"] = window[idx_t[:, None], slots[None, :]]
+    if diag is not None:
+        out["rhat"], out["n_eff"] = diag
+    for name, v in out.items():
+        v = v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
 def dry_run(a, world, rank):
     """The rank/offset logic of a real run, on CPU ranks (gloo): no GPU is touched."""
     import torch
@@ -422,7 +469,8 @@ def main():
     for _ in range(W):
         step(it)
         it += S
-    if window is not None and not a.no_ess and W > 0 and N >= 2:
+    do_ess = not a.no_ess and (a.full or sd is not None)   # the window's R-hat / ESS: a --full figure
+    if window is not None and do_ess and W > 0 and N >= 2:
         # warm-up of the post-run diagnostics too: the first launch of their kernels loads the code
         # object (~70 ms once per process); a 64-chain slice of the window has the same rows, so
         # the same lag-kernel instance (conv_tmax depends on the rows only).  Results discarded.
@@ -430,7 +478,7 @@ def main():
     torch.cuda.synchronize(dev)
     c0 = eng.read_counters()
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(K)]
-    tele = Telemetry(dev.index) if (rank == 0 and not a.no_telemetry) else None
+    tele = Telemetry(dev.index) if (rank == 0 and a.full and not a.no_telemetry) else None
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -459,7 +507,8 @@ def main():
     t_max, kern_max = reduce([elapsed, kern_ms], dist.ReduceOp.MAX if world > 1 else None)
     value = lf_all / t_max
     ess = None
-    if not a.no_ess:
+    R_hat = neff = None
+    if do_ess:
         grp = dist.group.WORLD if world > 1 else None
         torch.cuda.synchronize(dev)
         td = time.perf_counter()
@@ -487,6 +536,9 @@ def main():
                            f"reference estimator on the circular window's last {R} samples per chain (all chains), "
                            f"after the timed loop; ESS/s = n_eff / time of the {R} iterations that produced them "
                            f"(ess_per_s_median_incl_diag adds the diagnostics' own time)"))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, eng, window if store else (eng._stream[1] if sd is not None else None), K, S,
+                     offset, diag=(R_hat, neff) if sd is not None and do_ess else None)
     if world > 1:
         dist.destroy_process_group()
 
@@ -591,7 +643,7 @@ def main():
             "debug_env_unset": True,
             "ess": ess,
         }
-        if not a.no_cpu_baseline:       # rank 0 at any N, after every rank left the timed region
+        if a.full and not a.no_cpu_baseline:       # rank 0 at any N, after every rank left the timed region
             line["cpu_baseline"] = cpu_baseline(D, a.cpu_seconds, a.rho, a.sampler, a.d_max)
         print(json.dumps(line), flush=True)
 

@@ -34,7 +34,7 @@ do_bench() {   # bench args...
 
 do_prof() {    # bench args...
   local OUT="$R/gpurun_out/prof_$TAG"
-  local ARGS="--no-cpu-baseline --steps 10 --warmup 2 $*"
+  local ARGS="--full --no-cpu-baseline --steps 10 --warmup 2 $*"
   mkdir -p "$OUT"
   (cd /tmp &&
    timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- \
@@ -53,15 +53,15 @@ do_pmc() {     # "counters" bench args...
   local OUT="$R/gpurun_out/pmc_$TAG"
   mkdir -p "$OUT"
   (cd /tmp && timeout -s KILL 300 rocprofv3 --pmc $P --output-format csv -d "$OUT" -o run -- \
-     python3 "$R/bench.py" --no-cpu-baseline --steps 10 --warmup 2 "$@" > "$OUT/pmc.log" 2>&1) || return $?
+     python3 "$R/bench.py" --full --no-cpu-baseline --steps 10 --warmup 2 "$@" > "$OUT/pmc.log" 2>&1) || return $?
   python3 scripts/pmc_summary.py "$OUT" "k_" > "$OUT/summary.txt"
 }
 
 do_configs() {
   local T=$TAG
-  TAG=${T}_c3_dense;  do_bench --no-cpu-baseline --rho 0.95 --chains 262144 --steps 10 --warmup 2 || return $?
-  TAG=${T}_c5_nuts;   do_bench --no-cpu-baseline --sampler nuts --rho 0.95 --chains 65536 --steps 5 --warmup 1 || return $?
-  TAG=${T}_c4_d1000;  do_bench --no-cpu-baseline --dim 1000 --chains 131072 --stream-diag --steps 10 --warmup 2 || return $?
+  TAG=${T}_c3_dense;  do_bench --full --no-cpu-baseline --rho 0.95 --chains 262144 --steps 10 --warmup 2 || return $?
+  TAG=${T}_c5_nuts;   do_bench --full --no-cpu-baseline --sampler nuts --rho 0.95 --chains 65536 --steps 5 --warmup 1 || return $?
+  TAG=${T}_c4_d1000;  do_bench --full --no-cpu-baseline --dim 1000 --chains 131072 --stream-diag --steps 10 --warmup 2 || return $?
   TAG=${T}_c3_dense;  do_prof --rho 0.95 --chains 262144 || return $?
   TAG=${T}_c5_nuts;   do_prof --sampler nuts --rho 0.95 --chains 65536 --steps 5 --warmup 1 || return $?
   TAG=$T
@@ -82,7 +82,7 @@ case "$CMD" in
   prof) do_prof "$@" ;;
   pmc) do_pmc "$@" ;;
   configs) do_configs ;;
-  round) do_test && do_bench && do_prof ;;
+  round) do_test && do_bench --full && do_prof ;;
   ubench) do_ubench ;;
   *) echo "unknown command $CMD"; exit 2 ;;
 esac
