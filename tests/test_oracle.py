@@ -190,6 +190,53 @@ def test_nuts_closed_form_save_slots():
                 assert held.get(slot(int(l), d_max)) == int(l), (d_max, m, l)
 
 
+def _tree_host(d_max, depth):
+    """Output of csrc/nuts_tree_host.cpp (built by make next to libhmc.so): per point m of a
+    sub-tree of 2^depth points, ("s", slot) for an odd m, ("c", [(l, slot), ...]) for an even one."""
+    import os
+    import subprocess
+    from hmc_amd import _lib
+    exe = os.path.join(os.path.dirname(_lib.LIB_PATH), "nuts_tree_host")
+    assert os.path.exists(exe), f"{exe} not found: build it with make -C understanding-hmc_amd/csrc"
+    out = subprocess.run([exe, str(d_max), str(depth)], check=True, capture_output=True, text=True).stdout
+    pts = {}
+    for line in out.splitlines():
+        f = line.split()
+        pts[int(f[0])] = ("s", int(f[2])) if f[1] == "s" else \
+            ("c", [tuple(int(x) for x in t.split(":")) for t in f[2:]])
+    assert sorted(pts) == list(range(1, (1 << depth) + 1))
+    return pts
+
+
+def test_nuts_tree_header_save_slots_and_check_points():
+    """The same property as test_nuts_closed_form_save_slots, on the C++ the three NUTS kernels
+    compile (csrc/hmc_nuts_tree.hpp save_slot / CheckPoints, printed by the host program
+    nuts_tree_host): its check points equal check_points(m), and every one of them is still the
+    last point stored in its slot when m is reached.  d_max 1..12 with every d < d_max, and one
+    tree of 2^17 points at d_max = 30 (check_points compared on the points the Python test walks)."""
+    from hmc_amd.utils import check_points
+
+    def walk(d_max, depth, compare):
+        pts = _tree_host(d_max, depth)
+        held = {}
+        for m in range(1, (1 << depth) + 1):
+            kind, v = pts[m]
+            if m % 2:
+                assert kind == "s" and 0 <= v <= d_max, (d_max, depth, m, v)
+                assert v == (d_max if m == 1 else ((m - 1) & -(m - 1)).bit_length() - 1)
+                held[v] = m
+            else:
+                assert kind == "c"
+                if compare(m):
+                    assert [l for l, _ in v] == [int(l) for l in check_points(m)], (d_max, depth, m)
+                for l, s in v:
+                    assert held.get(s) == l, (d_max, depth, m, l, s)
+    for d_max in range(1, 13):
+        for d in range(d_max):
+            walk(d_max, d, lambda m: True)
+    walk(30, 17, lambda m: m & (m - 1) == 0 or m % 64 == 0 or m > (1 << 17) - 4096)
+
+
 def test_reference_nuts_drifts_with_a_mass_matrix():
     """A property of the reference the large-D NUTS tests rely on: with cov_p other than the
     identity, the reference's NUTS (Q3 leapfrog: kick by inv(cov_p).dVdq, drift by p; Q11 ratio;

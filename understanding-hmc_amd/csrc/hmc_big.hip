@@ -22,6 +22,7 @@
 #include "hmc_device.hpp"
 #include "hmc_internal.hpp"
 #include "hmc_dense_ops.hpp"
+#include "hmc_nuts_tree.hpp"   // stores_row: the row rule shared with the NUTS kernels
 
 namespace hmc {
 
@@ -39,10 +40,6 @@ __device__ __forceinline__ double grad_at(const BigArgs& b, int64_t i, int d, do
   const RandArgs& a = b.a;
   const double x = qd - q0_of(a, d);
   return a.prec ? a.prec[d] * x : x;
-}
-
-__device__ __forceinline__ bool write_row_of(const RandArgs& a, int it) {
-  return it >= a.wu && ((it == a.niter) || ((it - a.wu + 1) % a.thin == 0));
 }
 
 // chain-0 trajectory capture (samplers.py:442-452, :463-475; make_movie's input): global chain 0
@@ -98,7 +95,7 @@ __global__ __launch_bounds__(256) void k_big_begin(BigArgs b, int it) {
   kin = wave_sum_dpp(kin);
   const double E0 = 0.5 * (a.logc + (maha + kin));
   if (lane == 0) {
-    if (!MASS && write_row_of(a, it)) {                             // (full cov_p: k_big_energy)
+    if (!MASS && stores_row(a, it)) {                             // (full cov_p: k_big_energy)
       const int64_t row = c * (int64_t)a.Lc + (it - a.wu) / a.thin;
       if (a.Ec) a.Ec[row] = E0;
       if (a.dEc) a.dEc[row] = E0 - a.Eprev[c];
@@ -233,7 +230,7 @@ __global__ __launch_bounds__(256) void k_big_end(BigArgs b, int it) {
   const double lnu = b.lnu[c];
   const bool accept = (dE < 0.0) || (lnu < -dE);                    // :462
   const bool post = it >= a.wu;
-  const bool write_row = write_row_of(a, it);
+  const bool write_row = stores_row(a, it);
   const int64_t row = post ? (int64_t)((it - a.wu) / a.thin) : 0;
   const bool store = write_row && a.qc && row >= a.q_row0;
   double* rowp = store ? a.qc + c * (int64_t)a.Lq * D + (row % a.Lq) * D : nullptr;
@@ -284,7 +281,7 @@ __global__ __launch_bounds__(256) void k_big_energy(BigArgs b, int it) {
     if (a.Ec) a.Ec[c * (int64_t)a.Lc] = E0;
     if (a.dEc) a.dEc[c * (int64_t)a.Lc] = 0.0;
   } else {
-    if (write_row_of(a, it)) {
+    if (stores_row(a, it)) {
       const int64_t row = c * (int64_t)a.Lc + (it - a.wu) / a.thin;
       if (a.Ec) a.Ec[row] = E0;
       if (a.dEc) a.dEc[row] = E0 - a.Eprev[c];

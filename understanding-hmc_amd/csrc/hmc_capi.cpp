@@ -352,13 +352,19 @@ int64_t hmc_random_workspace_size(const hmc_target* t, int64_t n_chains) {
 int64_t hmc_nuts_workspace_size_ex(int32_t D, int64_t n_chains, int32_t d_max, int32_t iters_per_call,
                                    int32_t philox_momenta) {
   if (D < 1 || n_chains < 0 || d_max < 1 || d_max > hmc::kNutsDmaxMax || iters_per_call < 1) return 0;
-  if (hmc::nuts_lock_path(D)) {   // philox_momenta 0: replay tapes, or a full cov_p (its fragments too)
-    return (philox_momenta ? hmc::nuts_lock_ws_doubles(n_chains, D, d_max, false)
-                           : hmc::nuts_lock_ws_doubles(n_chains, D, d_max, true)) *
-           (int64_t)sizeof(double);
+  int64_t doubles = 0;
+  switch (hmc::nuts_kernel(D)) {
+    case hmc::NutsKernel::Tree:
+      doubles = hmc::nuts_ws_doubles(n_chains, D, d_max, philox_momenta ? iters_per_call : 0);
+      break;
+    case hmc::NutsKernel::Lock:   // philox_momenta 0: replay tapes, or a full cov_p (its fragments too)
+      doubles = hmc::nuts_lock_ws_doubles(n_chains, D, d_max, !philox_momenta);
+      break;
+    case hmc::NutsKernel::PerChain:
+      doubles = hmc::nuts_big_ws_doubles(n_chains, D, d_max);
+      break;
   }
-  if (!hmc::dense_tiles(D)) return hmc::nuts_big_ws_doubles(n_chains, D, d_max) * (int64_t)sizeof(double);
-  return hmc::nuts_ws_doubles(n_chains, D, d_max, philox_momenta ? iters_per_call : 0) * (int64_t)sizeof(double);
+  return doubles * (int64_t)sizeof(double);
 }
 
 int64_t hmc_nuts_workspace_size(int32_t D, int64_t n_chains, int32_t d_max) {
@@ -435,7 +441,6 @@ hmc_status hmc_nuts_iters(const hmc_target* t, const hmc_kinetic* k, const hmc_s
   if (s->d_max < 1 || s->d_max > hmc::kNutsDmaxMax) return fail(HMC_EINVAL, "d_max must be in [1, %d]", hmc::kNutsDmaxMax);
   if (hmc_status e = check_mass(t, k, s)) return e;
   if (t->kind != HMC_TARGET_DENSE) return fail(HMC_ENOTSUP, "NUTS runs the dense kernel: pass prec as dense");
-  const bool big = !hmc::dense_tiles(t->D);   // D > 128: hmc_nuts_big.hip
   const bool replay = s->rng_mode == HMC_RNG_REPLAY;
   if (replay && (!r || !r->p || !r->tape || r->tape_stride < 1)) return fail(HMC_EINVAL, "replay mode needs p and tape");
   if (s->n_chains == 0 || s->iter_end == s->iter_begin) return HMC_OK;
@@ -456,13 +461,16 @@ hmc_status hmc_nuts_iters(const hmc_target* t, const hmc_kinetic* k, const hmc_s
   }
   a.traj_q = nullptr;
   a.n_save = 0;
-  if (big && hmc::nuts_lock_path(t->D))   // 128 < D <= 320: lockstep 16-chain blocks (any cov_p)
-    return hip_status(hmc::launch_nuts_lock(a, s->fp_mode == HMC_MODE_EXACT, replay, (hipStream_t)stream),
-                      "hmc_nuts_iters(lockstep)");
-  if (big) return hip_status(hmc::launch_nuts_big(a, s->fp_mode == HMC_MODE_EXACT, replay, (hipStream_t)stream),
-                             "hmc_nuts_iters(large D)");
-  return hip_status(hmc::launch_nuts_iters(a, s->fp_mode == HMC_MODE_EXACT, replay, (hipStream_t)stream),
-                    "hmc_nuts_iters");
+  const bool exact = s->fp_mode == HMC_MODE_EXACT;
+  switch (hmc::nuts_kernel(t->D)) {
+    case hmc::NutsKernel::Lock:
+      return hip_status(hmc::launch_nuts_lock(a, exact, replay, (hipStream_t)stream), "hmc_nuts_iters(lockstep)");
+    case hmc::NutsKernel::PerChain:
+      return hip_status(hmc::launch_nuts_big(a, exact, replay, (hipStream_t)stream), "hmc_nuts_iters(large D)");
+    case hmc::NutsKernel::Tree:
+      break;
+  }
+  return hip_status(hmc::launch_nuts_iters(a, exact, replay, (hipStream_t)stream), "hmc_nuts_iters");
 }
 
 hmc_status hmc_leapfrog(const hmc_target* t, const hmc_kinetic* k, int64_t n, const double* p, const double* q,

@@ -82,6 +82,13 @@ bool nuts_lock_path(int D);
 int64_t nuts_lock_ws_doubles(int64_t n, int D, int d_max, bool mass);
 hipError_t launch_nuts_lock(const RandArgs& a, bool exact, bool replay, hipStream_t s);
 hipError_t launch_nuts_big(const RandArgs& a, bool exact, bool replay, hipStream_t s);
+// Which NUTS kernel runs dimension D: the MFMA tree kernel (hmc_nuts.hip) wherever the dense tile
+// fits, the lockstep blocks up to their limit, one wave per chain beyond.
+enum class NutsKernel { Tree, Lock, PerChain };
+inline NutsKernel nuts_kernel(int D) {
+  if (dense_tiles(D)) return NutsKernel::Tree;
+  return nuts_lock_path(D) ? NutsKernel::Lock : NutsKernel::PerChain;
+}
 
 Layout choose_layout(int D, int L_low, int L_high);
 

@@ -1,9 +1,11 @@
 // hmc_nuts.hip — the reference's NUTS engine (samplers.py:495-808, utils.py:222-385) for many chains.
 //
 // Semantics follow gen_sample_NUTS exactly (quirks Q10-Q12 of SURVEY §8-Q): doubling until BOTH
-// ends U-turn, sub-tree U-turn checks against the saved odd points named by check_points(m)
-// with release_fast bookkeeping, progressive multinomial sampling inside the new sub-tree,
-// biased sub-tree acceptance exp(-(Emax_new-Emax_old))*pi_old/pi_new, |E - E0| > 1000 guard.
+// ends U-turn, sub-tree U-turn checks against the saved odd points named by check_points(m),
+// progressive multinomial sampling inside the new sub-tree, biased sub-tree acceptance
+// exp(-(Emax_new-Emax_old))*pi_old/pi_new, |E - E0| > 1000 guard.  That per-chain scalar bookkeeping
+// (save slots, check points, weights, draws, row rule, counters) is hmc_nuts_tree.hpp, shared with
+// hmc_nuts_lock.hip and hmc_nuts_big.hip.
 //
 // Execution model: 16 chains per wave share the f64-MFMA gradient tile of hmc_dense_ops.hpp.
 // NUTS trees diverge per chain (7 ... 1023 leapfrogs per iteration), so each chain runs its own
@@ -20,11 +22,11 @@
 #include "hmc_dense_ops.hpp"
 #include "hmc_device.hpp"
 #include "hmc_internal.hpp"
+#include "hmc_nuts_tree.hpp"
 
 namespace hmc {
 
 namespace {
-
 
 // Waves per block (one block per CU: the LDS copy of P), one per SIMD with the whole register file.
 // 8 (two waves per SIMD, 256 registers each) was measured at 0.42x: the step spills ~560 B per lane
@@ -246,40 +248,6 @@ __device__ __forceinline__ void gload(const WaveWS& w, int v, int vl, d4 (&acc)[
   }
 }
 
-// Save slot of odd point l of a sub-tree.  The reference keeps the saved odd points in a table
-// (find_next / retrieve_save_index / release_fast, utils.py:222-385) and looks them up by value.
-// A saved point l is only ever checked as the first point of an aligned block of size s | (l - 1)
-// ending at an even point m <= l + lowbit(l - 1) - 1, so two points with the same level
-// ctz(l - 1) are never needed at the same time: slot = ctz(l - 1) (point 1, the start of every
-// block, gets slot d_max) holds exactly the points the table would hold when they are checked,
-// with no search and no releases.
-__device__ __forceinline__ int save_slot(int l, int d_max) { return l == 1 ? d_max : __builtin_ctz(l - 1); }
-
-// closed forms of utils.py check_points / release_fast (integer bit logic)
-__device__ __forceinline__ int cp_r(int m) {   // r of check_points(m): strip leading bits until pow2 or <= 2
-  int r = m;
-  while ((r & (r - 1)) != 0 && r > 2) r -= 1 << (31 - __builtin_clz(r));
-  return r;
-}
-__device__ __forceinline__ int cp_count(int m) {   // number of check points of even m
-  const int r = cp_r(m);
-  int cnt = 1, half = r;
-  while (half > 2) {
-    half >>= 1;
-    ++cnt;
-  }
-  return cnt;
-}
-__device__ __forceinline__ bool release_fast(int m, int l) {   // utils.py:367-385
-  int rm = m, rl = l;
-  while ((rm & (rm - 1)) != 0 && rm > 4) {
-    const int top = 1 << (31 - __builtin_clz(rm));
-    rm -= top;
-    rl -= top;
-  }
-  return (rm >= 4) && (rl > 1);
-}
-
 // acc + x*y: the reference's separate multiply and add in EXACT mode, one FMA in FAST mode (the
 // per-step dot products and energy sums: ~150 VALU per wave step).
 template <bool EXACT>
@@ -384,7 +352,7 @@ void k_nuts_iters(RandArgs a) {
   int it = a.it0;
   int d = 0, k = 0, Lsub = 1, udir = 0, ndraw = 0;
   bool lterm = false, rterm = false;
-  double E_init = 0.0, E_max_now = 0.0, E_max_old = 0.0, pi_new = 1.0, pi_old = 1.0;
+  double E_init = 0.0, E_max_now = 0.0, E_max_old = 0.0, pi_new = 1.0, pi_old = 1.0;   // TreeWeights
   int64_t tpos = 0;                                     // replay tape cursor (persists across launches)
   int old2 = 0;                                         // vector offset of the live_point_old pair
   unsigned long long n_lf = 0, n_unst = 0, n_dmax = 0, n_tape = 0, n_steps = 0, n_giveup = 0;
@@ -393,19 +361,10 @@ void k_nuts_iters(RandArgs a) {
   unsigned long long t_ph = __builtin_amdgcn_s_memtime(), t_sub = t_ph;
 #endif
 
-  auto draw = [&](bool direction) -> double {           // next random number of this chain (reference order)
-    if constexpr (REPLAY) {
-      if (tpos >= a.tape_stride) {                     // exhausted tape: flagged, host raises
-        ++n_tape;
-        return direction ? 0.0 : 2.0;
-      }
-      return a.tape[c * a.tape_stride + (tpos++)];
-    } else {
-      const uint4 r = draw_block(kDrawSlot + (uint32_t)(ndraw++), (uint32_t)it, gc, a.k0, a.k1);
-      return direction ? (double)(r.x & 1u) : u53(r.z, r.w);
-    }
+  auto draw = [&](bool direction) {                     // next random number of this chain (reference order)
+    if constexpr (REPLAY) return NutsDraws::tape(tpos, a, n_tape, c, direction);
+    else return NutsDraws::philox(ndraw, it, gc, a, direction);
   };
-  auto write_row_of = [&](int i) { return i >= a.wu && ((i == a.niter) || ((i - a.wu + 1) % a.thin == 0)); };
 
   while (true) {
     // ================= transitions (ITER_END -> ITER_START -> first doubling), converged reductions
@@ -420,7 +379,7 @@ void k_nuts_iters(RandArgs a) {
                                                         // takes the chain next (S_GRAD), so the live
                                                         // points keep no gradient vector
         const int qrow = (it - a.wu) / a.thin;
-        if (write_row_of(it) && a.qc && qrow >= a.q_row0) {
+        if (stores_row(a, it) && a.qc && qrow >= a.q_row0) {
           double* rowp = a.qc + (c * (int64_t)a.Lq + qrow % a.Lq) * a.D;
 #pragma unroll
           for (int m = 0; m < ME; ++m)
@@ -602,7 +561,7 @@ void k_nuts_iters(RandArgs a) {
       kin = chain_sum4(kin);
       if (starting) {                                   // E_initial (:569), E/dE storage (:571-573)
         E_init = 0.5 * (a.logc + (maha_old + kin));
-        if (write_row_of(it) && h == 0) {
+        if (stores_row(a, it) && h == 0) {
           const int64_t row = c * (int64_t)a.Lc + (it - a.wu) / a.thin;
           if (a.Ec) a.Ec[row] = E_init;
           if (a.dEc) a.dEc[row] = E_init - Eprev;
@@ -762,7 +721,7 @@ void k_nuts_iters(RandArgs a) {
     const int ncheck = checking && !reject ? cp_count(mpt) - 1 : 0;   // the saved check points
     const int ncheck_w = wave_max_i32(ncheck);
     bool alive_chk = ncheck > 0;
-    // check points of mpt, incrementally (cp_point): mpt - r + 1, then + r/2, + r/4, ...
+    // check points of mpt, incrementally (as CheckPoints): mpt - r + 1, then + r/2, + r/4, ...
     int cp_half = checking ? cp_r(mpt) : 2;
     int cp_pt = mpt - cp_half + 1;
     for (int ci = 0; ci < ncheck_w; ++ci) {
@@ -803,17 +762,10 @@ void k_nuts_iters(RandArgs a) {
     }
     NUTS_PHASE(5);
     if (later && !reject) {                             // progressive sampling (:743-751)
-      const double E_max_prev = E_max_now;
-      E_max_now = fmax(E_max_prev, E_tmp);
-      // exp(-(E_tmp - E_max_now)) and exp(E_max_now - E_max_prev): one argument is exactly 0
-      // (E_max_now is one of E_tmp, E_max_prev), so one exp and exp(0) = 1, as the reference
-      // (NaN energies give the same NaN r as the two exps)
-      const bool up = E_max_now != E_max_prev;
-      const double e = exp(up ? E_max_now - E_max_prev : -(E_tmp - E_max_now));
-      const double num = up ? 1.0 : e;
-      pi_new = num + (up ? e : 1.0) * pi_new;
-      const double r = num / pi_new;
-      if (draw(false) < r) {
+      const auto w = TreeWeights::add_point(E_max_now, pi_new, E_tmp);
+      E_max_now = w.E_max_now;
+      pi_new = w.pi_new;
+      if (draw(false) < w.r) {
         vstore<M, ME>(W, V_OLD_Q, 2 - old2, q);
         maha_new = maha_pt;
       }
@@ -841,12 +793,10 @@ void k_nuts_iters(RandArgs a) {
       vstore<M, ME>(W, 0, b, q);
       vstore<M, ME>(W, 1, b, p);
       gstore<MT, ME>(W, 2, b, acc);
-      const double r = exp(-(E_max_now - E_max_old)) * pi_old / pi_new;   // :766 (Q11)
-      const double E_max_old_prev = E_max_old;
-      E_max_old = fmax(E_max_old_prev, E_max_now);
-      pi_old = exp(-(E_max_now - E_max_old)) * pi_new + exp(-(E_max_old_prev - E_max_old)) * pi_old;
-      const double A = fmin(1.0, r);
-      if (draw(false) < A) {                            // :773-775: old <- new, as a buffer swap
+      const auto w = TreeWeights::merge(E_max_now, pi_new, E_max_old, pi_old);   // :766-771 (Q11)
+      E_max_old = w.E_max_old;
+      pi_old = w.pi_old;
+      if (draw(false) < w.A) {                            // :773-775: old <- new, as a buffer swap
         old2 = 2 - old2;
         maha_old = maha_new;
       }
@@ -902,8 +852,10 @@ void k_nuts_iters(RandArgs a) {
   n_dmax = wave_sum_u64(h == 0 ? n_dmax : 0ull);
   n_tape = wave_sum_u64(h == 0 ? n_tape : 0ull);
   n_giveup = wave_sum_u64(h == 0 ? n_giveup : 0ull);
+  // (written out, not nuts_flush_counters: skipping a zero n_steps, as that does, costs seven
+  // instances of this kernel scratch)
   if (lane == 0 && a.cnt) {
-    unsigned long long* cs = a.cnt + (wv & (HMC_COUNTER_SLOTS - 1)) * HMC_NCOUNTERS;
+    unsigned long long* cs = nuts_counter_row(a.cnt, wv);
     if (n_lf) {
       atomicAdd(cs + HMC_CNT_LEAPFROG, n_lf);
       atomicAdd(cs + HMC_CNT_ENERGY_EVALS, n_lf);
@@ -912,7 +864,7 @@ void k_nuts_iters(RandArgs a) {
     if (n_dmax) atomicAdd(cs + HMC_CNT_DMAX, n_dmax);
     if (n_tape) atomicAdd(cs + HMC_CNT_OOB_REJECT, n_tape);   // NUTS: replay tape exhausted
     if (n_giveup) atomicAdd(cs + HMC_CNT_HANDOFF_GIVEUP, n_giveup);   // broken chain hand-offs (must be 0)
-    atomicAdd(cs + HMC_CNT_LEAPFROG_SQ, n_steps);               // NUTS: wave steps (lane utilisation)
+    atomicAdd(cs + HMC_CNT_LEAPFROG_SQ, n_steps);               // wave steps: see nuts_flush_counters
   }
 }
 

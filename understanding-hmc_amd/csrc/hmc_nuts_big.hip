@@ -13,10 +13,10 @@
 // g) triples whose roles rotate when a sub-tree ends (:758-761), and the two live points swap
 // names when a sub-tree's point is accepted (:773-775).
 //
-// Draws: replay (momenta per iteration, a per-chain tape of directions / uniforms in consumption
-// order) or Philox keyed (slot, iteration, global chain) exactly as hmc_nuts.hip: momentum pair
-// slot 8j + h (h < 4) holds dims (8j + h, 8j + h + 4) through the table Box-Muller, tree draw n of
-// an iteration is block kDrawSlot + n (direction = bit 0 of x, uniform = u53(z, w)).
+// The tree's scalar bookkeeping (save slots, check points, sampling weights, draws, row rule,
+// counters) is hmc_nuts_tree.hpp, shared with the other two NUTS kernels.
+// Momenta: replay (one per iteration) or Philox keyed (slot, iteration, global chain) exactly as
+// hmc_nuts.hip: pair slot 8j + h (h < 4) holds dims (8j + h, 8j + h + 4) through the table Box-Muller.
 // This is a shape-range path (the c5 workload is D = 100, hmc_nuts.hip): per leapfrog it reads P
 // once per chain from L2 (D^2 * 8 bytes) instead of sharing it across a 16-chain MFMA tile.
 // 128 < D <= 320 with a diagonal cov_p runs the lockstep kernel (hmc_nuts_lock.hip) instead.
@@ -27,6 +27,7 @@
 // The triples then hold the kick vector in their g slot; P x lives in a per-chain scratch vector.
 #include "hmc_device.hpp"
 #include "hmc_internal.hpp"
+#include "hmc_nuts_tree.hpp"
 
 namespace hmc {
 
@@ -135,34 +136,6 @@ __device__ __forceinline__ void wave_copy(int D, const double* src, double* dst,
   for (int d = lane; d < D; d += kWave) dst[d] = src[d];
 }
 
-// utils.py:246-283 check_points(m) for even m as an iterator: the first point of every aligned
-// power-of-two sub-tree (size >= 2) ending at m, smallest start first
-struct CheckPoints {
-  int pt, half;
-  __device__ explicit CheckPoints(int m) {
-    int r = m;
-    while ((r & (r - 1)) != 0 && r > 2) r -= 1 << (31 - __builtin_clz(r));
-    pt = m - r + 1;
-    half = r;
-  }
-  __device__ bool next() {   // advance; false when done
-    if (half <= 2) return false;
-    half >>= 1;
-    pt += half;
-    return true;
-  }
-};
-
-// utils.py:367-385 release_fast(m, l)
-__device__ __forceinline__ bool release_fast(int m, int l) {
-  while ((m & (m - 1)) != 0 && m > 4) {
-    const int top = 1 << (31 - __builtin_clz(m));
-    m -= top;
-    l -= top;
-  }
-  return m >= 4 && l > 1;
-}
-
 template <bool EXACT, bool REPLAY, bool MASS>
 __global__ __launch_bounds__(256) void k_nuts_big(RandArgs a, int Dp, int nv) {
   __shared__ double tab[REPLAY ? 2 : kNormalTableDoubles];
@@ -186,19 +159,10 @@ __global__ __launch_bounds__(256) void k_nuts_big(RandArgs a, int Dp, int nv) {
   int it = 0;
   uint32_t ndraw = 0;
 
-  auto draw = [&](bool direction) -> double {          // next tree draw of this chain (reference order)
-    if constexpr (REPLAY) {
-      if (tpos >= a.tape_stride) {                      // exhausted tape: flagged, the host raises
-        ++n_tape;
-        return direction ? 0.0 : 2.0;
-      }
-      return a.tape[c * a.tape_stride + (tpos++)];
-    } else {
-      const uint4 r = draw_block(kDrawSlot + (ndraw++), (uint32_t)it, gc, a.k0, a.k1);
-      return direction ? (double)(r.x & 1u) : u53(r.z, r.w);
-    }
+  auto draw = [&](bool direction) {                    // next tree draw of this chain (reference order)
+    if constexpr (REPLAY) return NutsDraws::tape(tpos, a, n_tape, c, direction);
+    else return NutsDraws::philox(ndraw, it, gc, a, direction);
   };
-  auto write_row_of = [&](int i) { return i >= a.wu && ((i == a.niter) || ((i - a.wu + 1) % a.thin == 0)); };
 
   for (it = a.it0; it < a.it1; ++it) {
     // ---- iteration start (:563-584): p, E_initial, both ends (q, -p) / (q, p), live_q_old = q
@@ -234,12 +198,12 @@ __global__ __launch_bounds__(256) void k_nuts_big(RandArgs a, int Dp, int nv) {
     wave_grad<MASS>(a, tq(rgt), tg(rgt), gs, lane);
     wave_copy(D, tg(rgt), tg(lft), lane);
     const double E_init = wave_energy<MASS>(a, tq(rgt), tp(rgt), tg(rgt), gs, us, lane);   // :569
-    if (write_row_of(it) && lane == 0) {                                       // :571-573
+    if (stores_row(a, it) && lane == 0) {                                      // :571-573
       const int64_t row = c * (int64_t)a.Lc + (it - a.wu) / a.thin;
       if (a.Ec) a.Ec[row] = E_init;
       if (a.dEc) a.dEc[row] = E_init - Eprev;
     }
-    double E_max_old = E_init, pi_old = 1.0;
+    double E_max_old = E_init, pi_old = 1.0;                                   // TreeWeights
     bool lterm = false, rterm = false;
     ndraw = 0;
     for (int d = 0; !lterm || !rterm; ++d) {                                   // :595 (Q10)
@@ -247,26 +211,10 @@ __global__ __launch_bounds__(256) void k_nuts_big(RandArgs a, int Dp, int nv) {
         ++n_dmax;
         break;
       }
-      int table[kNutsDmaxMax + 1];                                             // :601 save-slot table
-#pragma unroll
-      for (int s = 0; s <= kNutsDmaxMax; ++s) table[s] = -1;
-      auto find_next = [&]() {                                                 // utils.py:222-228
-        int f = -1;
-#pragma unroll
-        for (int s = kNutsDmaxMax; s >= 0; --s)
-          if (s <= d_max && table[s] == -1) f = s;
-        return f;
-      };
-      auto set_slot = [&](int s, int v) {
-#pragma unroll
-        for (int i = 0; i <= kNutsDmaxMax; ++i)
-          if (i == s) table[i] = v;
-      };
-      auto save = [&](int v) {                                                 // q_save / p_save (:623-626)
-        const int s = find_next();
+      auto save = [&](int l) {                                                 // q_save / p_save (:623-626)
+        const int s = save_slot(l, d_max);
         wave_copy(D, tq(cur), W.v(kSave0 + 2 * s), lane);
         wave_copy(D, tp(cur), W.v(kSave0 + 2 * s + 1), lane);
-        set_slot(s, v);
       };
       const int L_new = 1 << d;
       const int udir = (int)draw(true);                                        // :608
@@ -292,11 +240,7 @@ __global__ __launch_bounds__(256) void k_nuts_big(RandArgs a, int Dp, int nv) {
         } else {                                                               // :699-736
           CheckPoints cp(k + 1);
           do {
-            const int l = cp.pt;
-            int s = 0;
-#pragma unroll
-            for (int i = kNutsDmaxMax; i >= 0; --i)                            // retrieve_save_index
-              if (table[i] == l) s = i;
+            const int s = save_slot(cp.pt, d_max);                             // :715
             const double* q_chk = W.v(kSave0 + 2 * s);
             const double* p_chk = W.v(kSave0 + 2 * s + 1);
             // udir 0: left = (q_chk, -p_chk), right = current; udir 1: left = current, right = (q_chk, -p_chk)
@@ -312,16 +256,13 @@ __global__ __launch_bounds__(256) void k_nuts_big(RandArgs a, int Dp, int nv) {
               reject = true;
               break;
             }
-            if (l > 1 && release_fast(k + 1, l)) set_slot(s, -1);
           } while (cp.next());
           if (reject) break;
         }
-        const double E_max_prev = E_max_now;                                   // :743-751
-        E_max_now = fmax(E_max_prev, E_tmp);
-        const double num = exp(-(E_tmp - E_max_now));
-        pi_new = num + exp(E_max_now - E_max_prev) * pi_new;
-        const double r_ = num / pi_new;
-        if (draw(false) < r_) wave_copy(D, tq(cur), W.v(nw), lane);
+        const auto w = TreeWeights::add_point<false>(E_max_now, pi_new, E_tmp);   // :743-751; two exps: see there
+        E_max_now = w.E_max_now;
+        pi_new = w.pi_new;
+        if (draw(false) < w.r) wave_copy(D, tq(cur), W.v(nw), lane);
       }
       if (reject) break;                                                       // :754-755
       if (udir == 0) {                                                         // :758-761
@@ -333,12 +274,10 @@ __global__ __launch_bounds__(256) void k_nuts_big(RandArgs a, int Dp, int nv) {
         lft = cur;
         cur = t;
       }
-      const double r_ = exp(-(E_max_now - E_max_old)) * pi_old / pi_new;       // :766 (Q11)
-      const double E_max_old_prev = E_max_old;
-      E_max_old = fmax(E_max_old_prev, E_max_now);
-      pi_old = exp(-(E_max_now - E_max_old)) * pi_new + exp(-(E_max_old_prev - E_max_old)) * pi_old;   // :771
-      const double A = fmin(1.0, r_);
-      if (draw(false) < A) {                                                   // :773-775
+      const auto w = TreeWeights::merge(E_max_now, pi_new, E_max_old, pi_old);   // :766-771 (Q11)
+      E_max_old = w.E_max_old;
+      pi_old = w.pi_old;
+      if (draw(false) < w.A) {                                                   // :773-775
         const int t = old;
         old = nw;
         nw = t;
@@ -350,7 +289,7 @@ __global__ __launch_bounds__(256) void k_nuts_big(RandArgs a, int Dp, int nv) {
     Eprev = E_init;
     const double* qf = W.v(old);
     const int qrow = (it - a.wu) / a.thin;
-    double* rowp = (write_row_of(it) && a.qc && qrow >= a.q_row0) ? a.qc + (c * (int64_t)a.Lq + qrow % a.Lq) * D
+    double* rowp = (stores_row(a, it) && a.qc && qrow >= a.q_row0) ? a.qc + (c * (int64_t)a.Lq + qrow % a.Lq) * D
                                                                   : nullptr;
     for (int d = lane; d < D; d += kWave) {
       const double qd = qf[d];
@@ -361,17 +300,7 @@ __global__ __launch_bounds__(256) void k_nuts_big(RandArgs a, int Dp, int nv) {
   if (lane == 0) {
     a.Eprev[c] = Eprev;
     if (REPLAY) tcur[c] = tpos;
-    if (a.cnt) {
-      unsigned long long* cs = a.cnt + (c & (HMC_COUNTER_SLOTS - 1)) * HMC_NCOUNTERS;
-      if (n_lf) {
-        atomicAdd(cs + HMC_CNT_LEAPFROG, n_lf);
-        atomicAdd(cs + HMC_CNT_ENERGY_EVALS, n_lf);
-        atomicAdd(cs + HMC_CNT_LEAPFROG_SQ, n_lf);   // NUTS: wave steps (one chain per wave here)
-      }
-      if (n_unst) atomicAdd(cs + HMC_CNT_UNSTABLE, n_unst);
-      if (n_dmax) atomicAdd(cs + HMC_CNT_DMAX, n_dmax);
-      if (n_tape) atomicAdd(cs + HMC_CNT_OOB_REJECT, n_tape);
-    }
+    nuts_flush_counters(a.cnt, c, n_lf, n_unst, n_dmax, n_tape, n_lf);
   }
 }
 

@@ -14,9 +14,9 @@
 //      fragments, prepared once per launch in the workspace, lane-linear: coalesced L2 reads) into
 //      contiguous fragment ranges and write their partial output tiles into LDS;
 //   3. barrier; each wave sums its chain's gradient rows from the partial tiles (fixed order) and
-//      finishes the step: second half kick, energy, the new point's bookkeeping (saves at slot
-//      ctz(l - 1), U-turn checks against check_points, progressive sampling), the sub-tree end
-//      (biased acceptance, termination).
+//      finishes the step: second half kick, energy, the new point's bookkeeping (saves, U-turn
+//      checks, progressive sampling), the sub-tree end (biased acceptance, termination): the scalar
+//      logic of hmc_nuts_tree.hpp, shared with the other two NUTS kernels.
 // A full cov_p (MASS, samplers.py:352-356, :811-839; round 6) adds block GEMMs on the same fragment
 // machinery, as the reference writes the products: the kick kv = inv_cov_p (P x) (a second GEMM on
 // the 16 gradients), K = p.inv_cov_p.p (a GEMM on the 16 momenta after the second half kick) and,
@@ -31,6 +31,7 @@
 
 #include "hmc_device.hpp"
 #include "hmc_internal.hpp"
+#include "hmc_nuts_tree.hpp"
 
 namespace hmc {
 
@@ -76,8 +77,6 @@ __global__ __launch_bounds__(256) void k_lock_pfrag(const double* __restrict__ p
 __device__ __forceinline__ int lock_f0(int w, int F) { return (int)(((int64_t)w * F) / kLockW); }
 
 typedef unsigned u32x2l __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ int save_slot_l(int l, int d_max) { return l == 1 ? d_max : __builtin_ctz(l - 1); }
 
 // J: coordinates per lane (D <= 64 J): instances J = 3 (D <= 192) and kLockJ, so that the
 // per-chain work of a smaller D issues no fully masked slots (and holds fewer registers)
@@ -174,23 +173,14 @@ __global__ __launch_bounds__(64 * kLockW) void k_nuts_lock(RandArgs a, LockGeom 
   int it = 0;
   int64_t tpos = 0;
   uint32_t ndraw = 0;
-  double Eprev = 0.0, E_init = 0.0, E_max_now = 0.0, E_max_old = 0.0, pi_new = 1.0, pi_old = 1.0;
+  double Eprev = 0.0, E_init = 0.0, E_max_now = 0.0, E_max_old = 0.0, pi_new = 1.0, pi_old = 1.0;   // TreeWeights
   int d = 0, k = 0, Lsub = 1, udir = 0, lo = LV_LIVE;       // lo: the live_old vector (the other is new)
   unsigned long long n_lf = 0, n_unst = 0, n_dmax = 0, n_tape = 0, n_steps = 0;
 
-  auto draw = [&](bool direction) -> double {               // next tree draw of this chain (reference order)
-    if constexpr (REPLAY) {
-      if (tpos >= a.tape_stride) {                          // exhausted tape: flagged, the host raises
-        ++n_tape;
-        return direction ? 0.0 : 2.0;
-      }
-      return a.tape[c * a.tape_stride + (tpos++)];
-    } else {
-      const uint4 r = draw_block(kDrawSlot + (ndraw++), (uint32_t)it, gc, a.k0, a.k1);
-      return direction ? (double)(r.x & 1u) : u53(r.z, r.w);
-    }
+  auto draw = [&](bool direction) {                         // next tree draw of this chain (reference order)
+    if constexpr (REPLAY) return NutsDraws::tape(tpos, a, n_tape, c, direction);
+    else return NutsDraws::philox(ndraw, it, gc, a, direction);
   };
-  auto write_row_of = [&](int i) { return i >= a.wu && ((i == a.niter) || ((i - a.wu + 1) % a.thin == 0)); };
   auto vstore = [&](int id, const double (&x)[J]) {
 #pragma unroll
     for (int j = 0; j < J; ++j) wput(id, j, x[j]);
@@ -459,7 +449,7 @@ __global__ __launch_bounds__(64 * kLockW) void k_nuts_lock(RandArgs a, LockGeom 
         p[j] = pd;
       }
       E_init = energy();                                    // :569
-      if (write_row_of(it) && lane == 0) {                  // :571-573
+      if (stores_row(a, it) && lane == 0) {                  // :571-573
         const int64_t row = c * (int64_t)a.Lc + (it - a.wu) / a.thin;
         if (a.Ec) a.Ec[row] = E_init;
         if (a.dEc) a.dEc[row] = E_init - Eprev;
@@ -508,8 +498,8 @@ __global__ __launch_bounds__(64 * kLockW) void k_nuts_lock(RandArgs a, LockGeom 
       vstore(LV_LIVE + LV_LIVE + 1 - lo, q);                // live_point_new
       E_max_now = E_tmp;
       pi_new = 1.0;
-      vstore(LV_SAVE + 2 * save_slot_l(1, d_max), q);
-      vstore(LV_SAVE + 2 * save_slot_l(1, d_max) + 1, p);
+      vstore(LV_SAVE + 2 * save_slot(1, d_max), q);
+      vstore(LV_SAVE + 2 * save_slot(1, d_max) + 1, p);
       k = 1;
       sub_end = Lsub == 1;
     } else {
@@ -517,15 +507,12 @@ __global__ __launch_bounds__(64 * kLockW) void k_nuts_lock(RandArgs a, LockGeom 
         reject = true;
         ++n_unst;
       } else if (m & 1) {                                   // odd point: save (:654-658)
-        const int s = save_slot_l(m, d_max);
+        const int s = save_slot(m, d_max);
         vstore(LV_SAVE + 2 * s, q);
         vstore(LV_SAVE + 2 * s + 1, p);
       } else {                                              // even point: U-turn checks (:699-736)
-        int r = m;
-        while ((r & (r - 1)) != 0 && r > 2) r -= 1 << (31 - __builtin_clz(r));
-        int pt = m - r + 1, half = r;
-        while (true) {
-          const int s = save_slot_l(pt, d_max);
+        for (CheckPoints cp(m);;) {
+          const int s = save_slot(cp.pt, d_max);
           double qc[J], pc[J];
           vload(LV_SAVE + 2 * s, qc);
           vload(LV_SAVE + 2 * s + 1, pc);
@@ -541,18 +528,14 @@ __global__ __launch_bounds__(64 * kLockW) void k_nuts_lock(RandArgs a, LockGeom 
             reject = true;
             break;
           }
-          if (half <= 2) break;
-          half >>= 1;
-          pt += half;
+          if (!cp.next()) break;
         }
       }
       if (!reject) {                                        // progressive sampling (:743-751)
-        const double E_max_prev = E_max_now;
-        E_max_now = fmax(E_max_prev, E_tmp);
-        const double num = exp(-(E_tmp - E_max_now));
-        pi_new = num + exp(E_max_now - E_max_prev) * pi_new;
-        const double r_ = num / pi_new;
-        if (draw(false) < r_) vstore(LV_LIVE + LV_LIVE + 1 - lo, q);
+        const auto w = TreeWeights::add_point<false>(E_max_now, pi_new, E_tmp);   // two exps: see there
+        E_max_now = w.E_max_now;
+        pi_new = w.pi_new;
+        if (draw(false) < w.r) vstore(LV_LIVE + LV_LIVE + 1 - lo, q);
         ++k;
         sub_end = k == Lsub;
       }
@@ -567,12 +550,10 @@ __global__ __launch_bounds__(64 * kLockW) void k_nuts_lock(RandArgs a, LockGeom 
       vstore(b, q);
       vstore(b + 1, p);
       vstore(b + 2, gslot());
-      const double r_ = exp(-(E_max_now - E_max_old)) * pi_old / pi_new;   // :766 (Q11)
-      const double E_max_old_prev = E_max_old;
-      E_max_old = fmax(E_max_old_prev, E_max_now);
-      pi_old = exp(-(E_max_now - E_max_old)) * pi_new + exp(-(E_max_old_prev - E_max_old)) * pi_old;   // :771
-      const double A = fmin(1.0, r_);
-      if (draw(false) < A) lo = LV_LIVE + LV_LIVE + 1 - lo; // :773-775 (names swap)
+      const auto w = TreeWeights::merge(E_max_now, pi_new, E_max_old, pi_old);   // :766-771 (Q11)
+      E_max_old = w.E_max_old;
+      pi_old = w.pi_old;
+      if (draw(false) < w.A) lo = LV_LIVE + LV_LIVE + 1 - lo; // :773-775 (names swap)
       bool rterm, lterm;                                    // :779-784 (Q10: both ends)
       if (udir == 0) {                                      // right = current
         rterm = span_dot(q, oq, p) < 0.0;
@@ -606,7 +587,7 @@ __global__ __launch_bounds__(64 * kLockW) void k_nuts_lock(RandArgs a, LockGeom 
       vload(lo, q);
       Eprev = E_init;
       const int qrow = (it - a.wu) / a.thin;
-      if (write_row_of(it) && a.qc && qrow >= a.q_row0) {
+      if (stores_row(a, it) && a.qc && qrow >= a.q_row0) {
         double* rowp = a.qc + (c * (int64_t)a.Lq + qrow % a.Lq) * D;
 #pragma unroll
         for (int j = 0; j < J; ++j)
@@ -627,17 +608,8 @@ __global__ __launch_bounds__(64 * kLockW) void k_nuts_lock(RandArgs a, LockGeom 
       }
     }
   }
-  if (lane == 0 && a.cnt) {
-    unsigned long long* cs = a.cnt + (((int64_t)blockIdx.x * kLockW + w) & (HMC_COUNTER_SLOTS - 1)) * HMC_NCOUNTERS;
-    if (n_lf) {
-      atomicAdd(cs + HMC_CNT_LEAPFROG, n_lf);
-      atomicAdd(cs + HMC_CNT_ENERGY_EVALS, n_lf);
-    }
-    if (n_steps) atomicAdd(cs + HMC_CNT_LEAPFROG_SQ, n_steps);   // NUTS: block steps (16 chain slots each)
-    if (n_unst) atomicAdd(cs + HMC_CNT_UNSTABLE, n_unst);
-    if (n_dmax) atomicAdd(cs + HMC_CNT_DMAX, n_dmax);
-    if (n_tape) atomicAdd(cs + HMC_CNT_OOB_REJECT, n_tape);
-  }
+  if (lane == 0)
+    nuts_flush_counters(a.cnt, (int64_t)blockIdx.x * kLockW + w, n_lf, n_unst, n_dmax, n_tape, n_steps);
 }
 
 // blocks of a launch: two chains per slot on average (small runs exercise the queue), at most one
