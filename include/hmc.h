@@ -179,6 +179,12 @@ hmc_status hmc_chain_init_ws(const hmc_target* t, const hmc_kinetic* k, const hm
 hmc_status hmc_random_iters_ws(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s,
                                const hmc_replay* r, hmc_state* st, int64_t order_bytes, void* stream);
 
+/* Which form of the leapfrog hmc_random_iters runs for these arguments (host-side query, no
+ * device access): 1 = the three-term recurrence u[n+1] = (2 - dt^2) u[n] - u[n-1] (FAST mode,
+ * wave-per-chain kernels, identity precision and mass, scalar dt with 1e-3 <= |dt| < 2), 0 = the
+ * kick/drift loops (every other case, EXACT mode included). */
+int32_t hmc_random_leapfrog_form(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s);
+
 /* Record the size of a scratch buffer (hmc_state.order or a NUTS workspace) for the unsized entry
  * points: a later call that would need more than `bytes` returns HMC_EINVAL instead of writing past
  * the end.  bytes = 0 forgets the buffer; a record stays until the pointer is registered again, so

@@ -1,7 +1,9 @@
 """Per-basic-block VALU / SALU / LDS / VMEM instruction counts of one kernel in a device .s file.
 
-    hipcc ... --offload-device-only -S -o /tmp/wave.s hmc_wave.hip
-    python scripts/dev/valu_blocks.py /tmp/wave.s 'k_wave_iters_k1ILb0ELb0ELb0ELb0ELb0E'
+    hipcc ... -DHMC_WAVE_PROD_ONLY --offload-device-only -S -o /tmp/wave.s hmc_wave.hip
+    python scripts/dev/valu_blocks.py /tmp/wave.s 'k_wave_iters_k1ILb0ELb0ELb0ELb0ELb0ELb1E'
+
+(the last template flag is TT: ...ELb1E the three-term leapfrog instance, ...ELb0E the two-FMA one)
 
 A static view for A/B work on instruction counts (the PMC SQ_INSTS_VALU pass is the measurement).
 """

@@ -105,6 +105,9 @@ hmc::RandArgs rand_args(const hmc_target* t, const hmc_kinetic* k, const hmc_sch
   a.k1 = (uint32_t)(s->seed >> 32);
   a.dt = k->dt;
   a.h = k->dt * 0.5;
+  a.lf_c = 2.0 - k->dt * k->dt;
+  a.lf_ch = 0.5 * a.lf_c;
+  a.lf_idt2 = 1.0 / (k->dt * k->dt);
   a.logc = t->logdet_const;
   a.q0 = t->q0;
   a.prec = t->prec;
@@ -335,6 +338,15 @@ hmc_status hmc_random_iters(const hmc_target* t, const hmc_kinetic* k, const hmc
     it = end;
   }
   return HMC_OK;
+}
+
+int32_t hmc_random_leapfrog_form(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s) {
+  if (!t || !k || !s || t->D < 1 || t->kind == HMC_TARGET_DENSE || hmc::big_path(false, t->D)) return 0;
+  const hmc::Layout lay = hmc::choose_layout(t->D, s->L_low, s->L_high);
+  if (lay.K == 0) return 0;
+  hmc::RandArgs a{};
+  a.dt = k->dt;
+  return hmc::leapfrog_three_term(a, lay, s->fp_mode == HMC_MODE_EXACT, general_diag(t, k)) ? 1 : 0;
 }
 
 int64_t hmc_random_workspace_size_ex(const hmc_target* t, const hmc_kinetic* k, int64_t n_chains) {

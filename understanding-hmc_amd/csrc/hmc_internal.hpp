@@ -25,6 +25,7 @@ struct RandArgs {
   int niter, wu, thin, Lc, L_low, L_high, it0, it1, i_oob;
   uint32_t k0, k1;       // Philox key (seed)
   double dt, h, logc;    // step, dt/2, V constant
+  double lf_c, lf_ch, lf_idt2;   // three-term leapfrog (scalar dt, identity target): 2 - dt^2, its half, 1/dt^2
   const double* q0;      // [D] or null
   const double* prec;    // [D] or null
   const double* minv;    // [D] or null
@@ -95,7 +96,12 @@ Layout choose_layout(int D, int L_low, int L_high);
 hipError_t launch_random_init(const RandArgs& a, const Layout& lay, bool gen, bool replay, hipStream_t s);
 hipError_t launch_random_iters(const RandArgs& a, const Layout& lay, bool exact, bool gen, bool replay,
                                hipStream_t s);
-hipError_t launch_wave_iters(const RandArgs& a, int K, bool exact, bool gen, bool replay, hipStream_t s);
+hipError_t launch_wave_iters(const RandArgs& a, int K, bool exact, bool gen, bool replay, bool three_term,
+                             hipStream_t s);
+// Whether launch_random_iters runs the FAST leapfrog in its three-term form (hmc_wave.hip, TT):
+// wave-per-chain layout, FAST mode, identity target and mass with a scalar dt inside the range
+// where recovering the momentum from the last two points is safe.
+bool leapfrog_three_term(const RandArgs& a, const Layout& lay, bool exact, bool gen);
 hipError_t launch_dense_init(const DenseArgs& a, bool replay, hipStream_t s);
 hipError_t launch_dense_iters(const DenseArgs& a, bool exact, bool replay, hipStream_t s);
 int64_t dense_order_ints(int64_t n);   // int32 scratch of the L-ordering (order[n] + histograms)

@@ -444,16 +444,40 @@ hipError_t launch_random_init(const RandArgs& a, const Layout& lay, bool gen, bo
   return hipErrorInvalidValue;
 }
 
-hipError_t launch_random_iters(const RandArgs& a, const Layout& lay, bool exact, bool gen, bool replay,
-                               hipStream_t s) {
+// The wave-per-chain kernels (hmc_wave.hip) serve this layout.
+static bool wave_layout(const Layout& lay) {
 #ifdef HMC_DEBUG_HOOKS
   const char* kern = getenv("HMC_KERNEL");       // experiments: "group" forces the lane-group kernel
   const bool force_group = kern && kern[0] == 'g';
 #else
   const bool force_group = false;
 #endif
-  if (lay.cpw == 1 && !force_group && (lay.K == 1 || lay.K == 2 || lay.K == 4 || lay.K == 8 || lay.K == 16))
-    return launch_wave_iters(a, lay.K, exact, gen, replay, s);
+  return lay.cpw == 1 && !force_group && (lay.K == 1 || lay.K == 2 || lay.K == 4 || lay.K == 8 || lay.K == 16);
+}
+
+// Three-term leapfrog u[n+1] = (2 - (dt w)^2) u[n] - u[n-1] (hmc_wave.hip, TT): the momentum comes
+// back as a difference of the last two points divided by dt, whose rounding error grows like
+// eps |u| / (dt w).  Lower bound: the smallest dt w at which the NumPy model of the kernel's
+// operation order keeps E within 1e-12 relative of a long-double integration over 19 steps at
+// D = 100 (tests/leapfrog_model.py energy_deviation; DESIGN.md 3.1: below 1e-12 from 4.6e-4 up,
+// the bound is set a factor 2 above that); upper bound: the integrator's stability limit
+// dt w = 2.  Outside the range the two-FMA loop runs.
+// -DHMC_NO_THREE_TERM builds the library that never picks it (A/B).
+bool leapfrog_three_term(const RandArgs& a, const Layout& lay, bool exact, bool gen) {
+#ifdef HMC_NO_THREE_TERM
+  return false;
+#else
+  constexpr double kThreeTermMinDtw = 1e-3;
+  if (exact || gen || !wave_layout(lay)) return false;
+  const double dtw2 = a.dt * a.dt;   // identity precision and mass: w = 1
+  return dtw2 >= kThreeTermMinDtw * kThreeTermMinDtw && dtw2 < 4.0;
+#endif
+}
+
+hipError_t launch_random_iters(const RandArgs& a, const Layout& lay, bool exact, bool gen, bool replay,
+                               hipStream_t s) {
+  if (wave_layout(lay))
+    return launch_wave_iters(a, lay.K, exact, gen, replay, leapfrog_three_term(a, lay, exact, gen), s);
   const dim3 grid = grid_for(a);
   switch (lay.K) {
     case 1: return launch_iters_k<1>(a, exact, gen, replay, grid, s);

@@ -59,6 +59,28 @@ __device__ __forceinline__ void wave_partials_fma(const double (&q)[2 * K], cons
   for (int e = 0; e < 2 * K; ++e) tot = __builtin_fma(p[e], p[e], tot);
 }
 
+// Three-term leapfrog steps as tied-register FMAs: each point is written over the one it retires
+// (r = c v - r), so the two alternating registers of a coordinate never need a move.
+__device__ __forceinline__ void tt_step(double& r, double c, double v) {
+  asm("v_fma_f64 %0, %1, %2, -%0" : "+v"(r) : "s"(c), "v"(v));
+}
+__device__ __forceinline__ void tt_first(double& r, double dt, double ph) {   // r += dt ph
+  asm("v_fma_f64 %0, %1, %2, %0" : "+v"(r) : "s"(dt), "v"(ph));
+}
+__device__ __forceinline__ void tt_start(double& r, double dt, double ph, double u0) {   // r = u0 - dt ph
+  asm("v_fma_f64 %0, -%1, %2, %3" : "+v"(r) : "s"(dt), "v"(ph), "v"(u0));
+}
+
+// x.x of this lane's coordinates, the FMA chain wave_partials_fma forms its potential part with
+template <int K>
+__device__ __forceinline__ double wave_sumsq_fma(const double (&v)[2 * K]) {
+  double s = v[1] * v[1];
+  s = __builtin_fma(v[0], v[0], s);
+#pragma unroll
+  for (int e = 2; e < 2 * K; ++e) s = __builtin_fma(v[e], v[e], s);
+  return s;
+}
+
 template <int K, bool GEN>
 __device__ __forceinline__ double kin_partial(const RandArgs& a, const int (&kk)[K], const bool (&pv)[K],
                                               const double (&p)[2 * K]) {
@@ -125,8 +147,11 @@ constexpr int kRingPairs = 128;
 // v_readlane/v_writelane VALU slot each, ~45 per iteration).
 // ODD: D is odd (the ring zeroes the missing coordinate of the last pair); a template parameter so
 // that the common even-D kernel carries no per-pass test.
-template <int K, bool EXACT, bool GEN, bool REPLAY, bool FULL, bool ODD = false>
+// TT: the FAST identity-target leapfrog in its three-term (Störmer) form, one FMA per coordinate
+// per step (the host picks it where the momentum recovery is safe: leapfrog_three_term, hmc_random.hip).
+template <int K, bool EXACT, bool GEN, bool REPLAY, bool FULL, bool ODD = false, bool TT = false>
 __device__ __forceinline__ void wave_iters(const RandArgs& a) {
+  static_assert(!TT || (!EXACT && !GEN), "the three-term leapfrog serves the FAST identity-target kernels only");
 #ifdef HMC_NO_RING
   constexpr bool RING = false;
 #else
@@ -352,7 +377,62 @@ __device__ __forceinline__ void wave_iters(const RandArgs& a) {
     // carried to the next iteration, and the back edge needs no moves
 #pragma unroll
     for (int e = 0; e < 2 * K; ++e) asm("v_mov_b64 %0, %1" : "=v"(qi[e]) : "v"(q[e]));
-    if constexpr (EXACT) {
+    double m1 = 0.0, k1 = 0.0, m1l = 0.0, s2 = 0.0;
+    if constexpr (TT) {
+      // FAST, identity target, three-term form: eliminating p from drift + merged kick gives
+      //   u[n+1] = c u[n] - u[n-1],  c = 2 - dt^2          (1 FMA per coordinate per step)
+      // with u[1] = u[0] + dt (p[0] - dt/2 u[0]): the same trajectory points, other rounding.
+      // p is needed once, after step L, for the kinetic energy alone (the next momentum is a fresh
+      // draw): w = dt p[L] = (c/2) u[L] - u[L-1], and q.q + p.p = fma(sum w^2, 1/dt^2, sum u^2).
+      // Two registers alternate as the newest point (interior steps in pairs, tied-register FMAs),
+      // u[L] always ends in q and u[L-1] in x: no moves beyond the start point's copy.  x takes
+      // p's registers (p is dead once the first step has read it, and the lanes and slots that sit
+      // the integration out hold the zeros the partials need there).
+      double (&x)[2 * K] = p;
+      if (L > 0) {
+        auto capture = [&](int l, const double (&v)[2 * K]) {
+          if (cap && lane == 0) {
+            capp[2 * (l + 1)] = v[0];
+            capp[2 * (l + 1) + 1] = a.D > 1 ? v[1] : v[0];
+          }
+        };
+        // The parity of L picks the starting pair, (u[0], u[1]) or (u[-1], u[0]), through scalar
+        // selects of the step: t = p -/+ dt/2 u[0], x = u[0] - sx t, q = u[0] + sq t with one of
+        // sx, sq zero.  (A branch on the parity inside the lanes' EXEC region is structurised into
+        // a form that keeps the start point live through both arms and costs the moves back.)
+        // (K = 1: lanes past npairs hold q = p = 0 and sit the integration out with EXEC off)
+        // (the selects stay scalar and read only dt and dt/2: no negated copies to keep in SGPRs)
+        const bool odd = (L & 1) != 0;
+        const double sh = __longlong_as_double(__double_as_longlong(a.h) ^ ((long long)(L & 1) << 63));   // -/+ dt/2
+        const double sx = odd ? 0.0 : a.dt, sq = odd ? a.dt : 0.0;
+        if (K > 1 || lane < a.npairs) {
+#pragma unroll
+          for (int e = 0; e < 2 * K; ++e) {
+            const double t = __builtin_fma(sh, q[e], p[e]);
+            tt_start(x[e], sx, t, q[e]);                  // u[0] (odd L) or u[-1] = u[0] - dt t
+            tt_first(q[e], sq, t);                        // u[1] = u[0] + dt t (odd L) or u[0]
+          }
+          if (odd) capture(0, q);
+          for (int l = L & 1; l < L; l += 2) {            // two steps: (u[l-1], u[l]) -> (u[l+1], u[l+2])
+#pragma unroll
+            for (int e = 0; e < 2 * K; ++e) tt_step(x[e], a.lf_c, q[e]);
+            capture(l, x);
+#pragma unroll
+            for (int e = 0; e < 2 * K; ++e) tt_step(q[e], a.lf_c, x[e]);
+            capture(l + 1, q);
+          }
+        }
+        // E1's partials from u[L] (in q) and u[L-1] (in x); every lane (idle ones add zeros)
+        double w[2 * K];
+#pragma unroll
+        for (int e = 0; e < 2 * K; ++e) w[e] = __builtin_fma(a.lf_ch, q[e], -x[e]);
+        m1l = wave_sumsq_fma<K>(q);
+        k1 = __builtin_fma(wave_sumsq_fma<K>(w), a.lf_idt2, m1l);
+      } else {                                            // no step: q and p are the start's
+        m1l = m0l;
+        k1 = e0l;
+      }
+    } else if constexpr (EXACT) {
       double t[2 * K];
 #pragma unroll
       for (int j = 0; j < K; ++j) {
@@ -434,9 +514,8 @@ __device__ __forceinline__ void wave_iters(const RandArgs& a) {
 
     // FASTID: E1's partials and the iteration's one reduction first; p is then dead, so the next
     // momentum is drawn into p itself (no copy at the end of the iteration)
-    double m1 = 0.0, k1 = 0.0, m1l = 0.0, s2 = 0.0;
     if constexpr (FASTID) {
-      wave_partials_fma<K>(q, p, m1l, k1);
+      if constexpr (!TT) wave_partials_fma<K>(q, p, m1l, k1);   // (TT formed them from the last two points)
       m1 = m1l;
       s2 = wave_sum2_dpp(k1 - e0l, e0l);   // lane 31: 2 (E1 - E0); lane 63: 2 E0 - logc
       E0 = __builtin_fma(s2, 0.5, hlogc);  // E0 of this iteration (lane 63)
@@ -559,71 +638,79 @@ __device__ __forceinline__ void wave_iters(const RandArgs& a) {
 
 // K = 1 (D <= 128, the headline shape) fits 64 VGPRs without spills: 8 waves per SIMD hide the
 // dependent-latency part of the loop (+4%); wider K keep the compiler's register budget.
-template <int K, bool EXACT, bool GEN, bool REPLAY, bool FULL>
+template <int K, bool EXACT, bool GEN, bool REPLAY, bool FULL, bool TT>
 __global__ __launch_bounds__(256) void k_wave_iters(RandArgs a) {
-  wave_iters<K, EXACT, GEN, REPLAY, FULL>(a);
+  wave_iters<K, EXACT, GEN, REPLAY, FULL, false, TT>(a);
 }
 
-template <bool EXACT, bool GEN, bool REPLAY, bool FULL, bool ODD>
+template <bool EXACT, bool GEN, bool REPLAY, bool FULL, bool ODD, bool TT>
 __global__ __launch_bounds__(kK1Block) __attribute__((amdgpu_waves_per_eu(8))) void k_wave_iters_k1(RandArgs a) {
-  wave_iters<1, EXACT, GEN, REPLAY, FULL, ODD>(a);
+  wave_iters<1, EXACT, GEN, REPLAY, FULL, ODD, TT>(a);
 }
 
-template <int K, bool EXACT, bool GEN, bool REPLAY>
+template <int K, bool EXACT, bool GEN, bool REPLAY, bool TT>
 void launch_wave_one(const RandArgs& a, dim3 grid, hipStream_t s) {
   const bool full = a.traj_q != nullptr || a.dbg != 0 || a.dbgL >= 0;
   if constexpr (K == 1) {
     const dim3 g1((unsigned)((a.n + kK1Block / kWave - 1) / (kK1Block / kWave)));
     const bool odd = (a.D & 1) != 0 && !REPLAY;   // only the ring (Philox) path specialises on odd D
     if (full) {
-      if (odd) k_wave_iters_k1<EXACT, GEN, REPLAY, true, !REPLAY><<<g1, kK1Block, 0, s>>>(a);
-      else k_wave_iters_k1<EXACT, GEN, REPLAY, true, false><<<g1, kK1Block, 0, s>>>(a);
+      if (odd) k_wave_iters_k1<EXACT, GEN, REPLAY, true, !REPLAY, TT><<<g1, kK1Block, 0, s>>>(a);
+      else k_wave_iters_k1<EXACT, GEN, REPLAY, true, false, TT><<<g1, kK1Block, 0, s>>>(a);
     } else {
-      if (odd) k_wave_iters_k1<EXACT, GEN, REPLAY, false, !REPLAY><<<g1, kK1Block, 0, s>>>(a);
-      else k_wave_iters_k1<EXACT, GEN, REPLAY, false, false><<<g1, kK1Block, 0, s>>>(a);
+      if (odd) k_wave_iters_k1<EXACT, GEN, REPLAY, false, !REPLAY, TT><<<g1, kK1Block, 0, s>>>(a);
+      else k_wave_iters_k1<EXACT, GEN, REPLAY, false, false, TT><<<g1, kK1Block, 0, s>>>(a);
     }
   } else {
-    if (full) k_wave_iters<K, EXACT, GEN, REPLAY, true><<<grid, 256, 0, s>>>(a);
-    else k_wave_iters<K, EXACT, GEN, REPLAY, false><<<grid, 256, 0, s>>>(a);
+    if (full) k_wave_iters<K, EXACT, GEN, REPLAY, true, TT><<<grid, 256, 0, s>>>(a);
+    else k_wave_iters<K, EXACT, GEN, REPLAY, false, TT><<<grid, 256, 0, s>>>(a);
   }
 }
 
+// tt (three-term leapfrog) only exists for the FAST identity-target instances
 template <int K, bool EXACT>
-hipError_t launch_wave_k2(const RandArgs& a, bool gen, bool replay, dim3 grid, hipStream_t s) {
+hipError_t launch_wave_k2(const RandArgs& a, bool gen, bool replay, bool tt, dim3 grid, hipStream_t s) {
   if (gen) {
-    if (replay) launch_wave_one<K, EXACT, true, true>(a, grid, s);
-    else launch_wave_one<K, EXACT, true, false>(a, grid, s);
+    if (replay) launch_wave_one<K, EXACT, true, true, false>(a, grid, s);
+    else launch_wave_one<K, EXACT, true, false, false>(a, grid, s);
+  } else if (!EXACT && tt) {
+    if (replay) launch_wave_one<K, EXACT, false, true, !EXACT>(a, grid, s);
+    else launch_wave_one<K, EXACT, false, false, !EXACT>(a, grid, s);
   } else {
-    if (replay) launch_wave_one<K, EXACT, false, true>(a, grid, s);
-    else launch_wave_one<K, EXACT, false, false>(a, grid, s);
+    if (replay) launch_wave_one<K, EXACT, false, true, false>(a, grid, s);
+    else launch_wave_one<K, EXACT, false, false, false>(a, grid, s);
   }
   return hipGetLastError();
 }
 
 template <int K>
-hipError_t launch_wave_k(const RandArgs& a, bool exact, bool gen, bool replay, dim3 grid, hipStream_t s) {
-  return exact ? launch_wave_k2<K, true>(a, gen, replay, grid, s) : launch_wave_k2<K, false>(a, gen, replay, grid, s);
+hipError_t launch_wave_k(const RandArgs& a, bool exact, bool gen, bool replay, bool tt, dim3 grid, hipStream_t s) {
+  return exact ? launch_wave_k2<K, true>(a, gen, replay, tt, grid, s)
+               : launch_wave_k2<K, false>(a, gen, replay, tt, grid, s);
 }
 
 }  // namespace
 
-hipError_t launch_wave_iters(const RandArgs& a, int K, bool exact, bool gen, bool replay, hipStream_t s) {
+hipError_t launch_wave_iters(const RandArgs& a, int K, bool exact, bool gen, bool replay, bool three_term,
+                             hipStream_t s) {
 #ifdef HMC_WAVE_PROD_ONLY   // dev: ISA inspection of the headline instance only (seconds to compile)
   if (K == 1 && !exact && !gen && !replay) {
-    launch_wave_one<1, false, false, false>(a, dim3(1), s);
+    if (three_term) launch_wave_one<1, false, false, false, true>(a, dim3(1), s);
+    else launch_wave_one<1, false, false, false, false>(a, dim3(1), s);
     return hipGetLastError();
   }
   return hipErrorInvalidValue;
-#endif
+#else
   const dim3 grid((unsigned)((a.n + 3) / 4));
   switch (K) {
-    case 1: return launch_wave_k<1>(a, exact, gen, replay, grid, s);
-    case 2: return launch_wave_k<2>(a, exact, gen, replay, grid, s);
-    case 4: return launch_wave_k<4>(a, exact, gen, replay, grid, s);
-    case 8: return launch_wave_k<8>(a, exact, gen, replay, grid, s);
-    case 16: return launch_wave_k<16>(a, exact, gen, replay, grid, s);
+    case 1: return launch_wave_k<1>(a, exact, gen, replay, three_term, grid, s);
+    case 2: return launch_wave_k<2>(a, exact, gen, replay, three_term, grid, s);
+    case 4: return launch_wave_k<4>(a, exact, gen, replay, three_term, grid, s);
+    case 8: return launch_wave_k<8>(a, exact, gen, replay, three_term, grid, s);
+    case 16: return launch_wave_k<16>(a, exact, gen, replay, three_term, grid, s);
   }
   return hipErrorInvalidValue;
+#endif
 }
 
 }  // namespace hmc
