@@ -254,6 +254,48 @@ hmc_status hmc_leapfrog(const hmc_target* t, const hmc_kinetic* k, int64_t n, co
 hmc_status hmc_energy(const hmc_target* t, const hmc_kinetic* k, int64_t n, const double* q,
                       const double* p, double* E_out, void* stream);
 
+/* ---------------------------------------------------------------- Gaussian-mixture target
+ * V(q) = -log sum_k w_k N(q; mu_k, diag var_k): a target that is not a multivariate normal, for
+ * the Random-trajectory sampler (the reference's HMC_sampler takes any V / dVdq closures,
+ * samplers.py:310-328).  With l_k = logw_k - 0.5 (logdet_const_k + sum_d prec_kd (q_d - mu_kd)^2),
+ * M = max_k l_k and S = sum_k exp(l_k - M):  V = -(M + log S),
+ * dV/dq_d = sum_k (exp(l_k - M) / S) prec_kd (q_d - mu_kd)  (hmc_mix.hip). */
+enum { HMC_MIX_MAX_COMPONENTS = 8, HMC_MIX_MAX_D = 512 };
+typedef struct hmc_mixture {
+  int32_t D, K;                /* 1 <= D <= HMC_MIX_MAX_D, 1 <= K <= HMC_MIX_MAX_COMPONENTS */
+  const double* logw;          /* [K]    log weights (weights sum to 1)                       */
+  const double* mu;            /* [K][D] component means                                      */
+  const double* prec;          /* [K][D] 1/variance of each component and dimension           */
+  const double* logdet_const;  /* [K]    D*log(2 pi) + sum_d log var_kd                       */
+} hmc_mixture;                 /* device pointers; 40 bytes */
+
+/* hmc_chain_init / hmc_random_iters for a mixture target: gen_sample_random, samplers.py:387-491,
+ * with the leapfrog and energies of :811-839 (Q3 semantics, as the diagonal MVN kernels).
+ * hmc_kinetic, hmc_schedule, hmc_replay and hmc_state mean exactly what they mean there: replay and
+ * Philox modes, chain_offset, iter_begin / iter_end, the circular window qc_rows / qc_row0, the
+ * n_save capture of chain 0, the counters ACCEPT, ACCEPT_WU, LEAPFROG, LEAPFROG_SQ (sum of L^2) and
+ * OOB_REJECT.  hmc_state.order is ignored.  schedule.fp_mode may be either value: there is one
+ * arithmetic (exp and log are ~1 ulp fp64, which cannot be bit-identical to NumPy's, so no EXACT
+ * form exists).  Philox draws are the lane-group kernel's at every D: momentum pair k of (chain,
+ * iteration it; it = 0 is the initial draw) is the plain Box-Muller of block (k, it, chain) scaled
+ * by p_scale, (L, u) come from block (0x80000000, it, chain); results do not depend on the layout,
+ * the launch split or the number of GPUs.
+ * HMC_EINVAL: null mu / prec / logw / logdet_const, D < 1, K < 1.  HMC_ENOTSUP: D > HMC_MIX_MAX_D,
+ * K > HMC_MIX_MAX_COMPONENTS, or a full cov_p (minv_full, p_chol_t or kick non-NULL); the diagonal
+ * minv, p_scale and dt_vec are supported. */
+hmc_status hmc_mix_chain_init(const hmc_mixture* m, const hmc_kinetic* k, const hmc_schedule* s,
+                              const hmc_replay* r /* NULL for Philox */, const double* q_start, hmc_state* st,
+                              void* stream);
+hmc_status hmc_mix_random_iters(const hmc_mixture* m, const hmc_kinetic* k, const hmc_schedule* s,
+                                const hmc_replay* r /* NULL for Philox */, hmc_state* st, void* stream);
+
+/* Batched single leapfrog step and total energy of n rows on a mixture target (one row per lane
+ * group): HMC_sampler.leap_frog, samplers.py:831-839, and E / K, :811-823. */
+hmc_status hmc_mix_leapfrog(const hmc_mixture* m, const hmc_kinetic* k, int64_t n, const double* p,
+                            const double* q, double* p_out, double* q_out, void* stream);
+hmc_status hmc_mix_energy(const hmc_mixture* m, const hmc_kinetic* k, int64_t n, const double* q,
+                          const double* p, double* E_out, void* stream);
+
 /* The standard normals the Philox mode draws for (chain, iteration): out[n][2*npairs].
  * Debug/verification entry (statistical tests of the in-kernel generator). */
 hmc_status hmc_rng_normals(uint64_t seed, int64_t chain0, int64_t n, int32_t iteration,

@@ -1,0 +1,381 @@
+"""Gaussian-mixture target on the GPU (csrc/hmc_mix.hip) against the CPU oracle.
+
+The oracle target (`OracleMixture`) is written here, directly from
+    l_k = log w_k - 0.5 (D log 2 pi + sum_d log var_kd + sum_d (q_d - mu_kd)^2 / var_kd)
+    V = -(M + log sum_k exp(l_k - M)),  dV/dq_d = sum_k softmax(l)_k (q_d - mu_kd) / var_kd
+and independently of hmc_amd.target.MixtureTarget; oracle/hmc_oracle.py's HMCCore and
+gen_sample_random run it unchanged.
+
+A bimodal potential amplifies rounding, so every parity case first asserts, on the oracle alone,
+three conditions on its INPUTS (not tolerances on the kernel): (1) no Metropolis decision is within
+1e-6 of flipping, (2) the oracle rerun from q_start (1 + 1e-13) moves q_chain by at most 1e-11, and
+(3) 5 % - 60 % of proposals are rejected and some chain changes its nearest component.
+"""
+import functools
+
+import numpy as np
+import pytest
+import torch
+from scipy.stats import norm
+
+from oracle import hmc_oracle as O
+from philox_host import bm_pair, host_L_lnu, words
+
+pytestmark = pytest.mark.gpu
+
+
+class OracleMixture:
+    def __init__(self, w, mu, var):
+        self.w, self.mu, self.var = np.asarray(w, float), np.asarray(mu, float), np.asarray(var, float)
+        self.q0 = np.zeros(self.mu.shape[1])         # HMCCore reads the dimension from q0
+
+    def _l(self, q):
+        D = self.mu.shape[1]
+        return np.log(self.w) - 0.5 * (D * np.log(2 * np.pi) + np.sum(np.log(self.var), axis=1)
+                                       + np.sum((q - self.mu) ** 2 / self.var, axis=1))
+
+    def V(self, q):
+        l = self._l(q)
+        M = l.max()
+        return -(M + np.log(np.sum(np.exp(l - M))))
+
+    def dVdq(self, q):
+        l = self._l(q)
+        e = np.exp(l - l.max())
+        return np.sum((e / e.sum())[:, None] * (q - self.mu) / self.var, axis=0)
+
+
+class RecordingCore(O.HMCCore):
+    """HMCCore that keeps every energy it returns: gen_sample_random asks for one per chain start and
+    then (E_init, E_final) per iteration, which gives each proposal's dE."""
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.energies = []
+
+    def E(self, q, p):
+        e = super().E(q, p)
+        self.energies.append(e)
+        return e
+
+
+#        D   K  N  Niter wu thin L_low L_high dt   seed sep dt_vec cov_p
+CASES = {
+    "A": (2, 2, 5, 12, 4, 1, 5, 20, 0.7, 11, 3, False, False),
+    "B": (37, 3, 4, 40, 7, 2, 5, 20, 0.4, 2, 3, True, True),       # dt vector + diagonal cov_p
+    "C": (100, 4, 3, 30, 0, 1, 5, 20, 0.45, 3, 4, False, False),
+    "D": (130, 8, 3, 30, 5, 3, 5, 20, 0.4, 4, 4, False, False),
+    "E": (1, 2, 6, 40, 0, 1, 1, 6, 0.8, 5, 2, False, False),       # D = 1 (exempt from the rejection floor)
+    "F": (64, 5, 4, 20, 3, 1, 5, 20, 0.45, 6, 3, False, False),    # lane-group boundary
+    "G": (65, 2, 4, 20, 3, 1, 5, 20, 0.4, 7, 3, False, True),      # first one-wave-per-chain size
+    "H": (512, 8, 2, 10, 0, 1, 5, 12, 0.3, 8, 5, False, False),    # ABI limit
+}
+
+
+def recipe(name, N=None, Niter=None):
+    """The shared input recipe, every draw from one RandomState(seed) in this order: weights,
+    means, variances, start points, Z0, Z, L, log u, then the optional dt vector and cov_p."""
+    D, K, N_, Niter_, wu, thin, Llo, Lhi, dt, seed, sep, dtvec, covp = CASES[name]
+    N, Niter = N or N_, Niter or Niter_
+    rs = np.random.RandomState(seed)
+    w = rs.uniform(0.5, 1.5, K)
+    w /= w.sum()
+    mu = rs.standard_normal((K, D))
+    mu *= sep / np.linalg.norm(mu, axis=1, keepdims=True)
+    var = rs.uniform(0.5, 2.0, (K, D))
+    q_start = mu[rs.randint(K, size=N)] + rs.standard_normal((N, D))
+    Z0 = rs.standard_normal((N, D))
+    Z = rs.standard_normal((N, Niter, D))
+    L = rs.randint(Llo, Lhi, size=(N, Niter)).astype(np.int32)
+    lnu = np.log(rs.random_sample((N, Niter)))
+    dt_ = dt * rs.uniform(0.7, 1.3, D) if dtvec else dt
+    cov_p = np.diag(rs.uniform(0.9, 1.1, D)) if covp else None
+    sd = np.sqrt(np.diag(cov_p)) if covp else 1.0
+    return dict(D=D, K=K, N=N, Niter=Niter, wu=wu, thin=thin, Llo=Llo, Lhi=Lhi, dt=dt_, cov_p=cov_p, w=w, mu=mu,
+                var=var, q_start=q_start, p0=Z0 * sd, P=Z * sd, L=L, lnu=lnu, sd=sd, seed=seed)
+
+
+def oracle_run(c, q_start=None, n_save=0):
+    core = RecordingCore(OracleMixture(c["w"], c["mu"], c["var"]), c["dt"], c["cov_p"])
+    out = O.gen_sample_random(core, c["q_start"] if q_start is None else q_start, c["N"], c["Niter"], c["wu"],
+                              c["thin"], c["Llo"], c["Lhi"], O.ReplayDraws(c["p0"], c["P"], c["L"], c["lnu"]),
+                              n_save_chain0=n_save)
+    E = np.asarray(core.energies).reshape(c["N"], 1 + 2 * c["Niter"])
+    out["dE_prop"] = E[:, 2::2] - E[:, 1::2]          # (N, Niter): E_final - E_init of every proposal
+    return out
+
+
+def check_input_conditions(c, ref, reject_floor=True):
+    """The three conditions of the module docstring; prints each figure before asserting it."""
+    dE, lnu = ref["dE_prop"], c["lnu"]
+    up = dE >= 0
+    margin = np.abs(lnu + dE)[up].min() if up.any() else np.inf
+    pert = oracle_run(c, q_start=c["q_start"] * (1 + 1e-13))
+    sens = np.abs(pert["q_chain"] - ref["q_chain"]).max()
+    rejected = int(np.sum(~((dE < 0) | (lnu < -dE))))
+    frac = rejected / dE.size
+    near = np.argmin(((ref["q_chain"][:, :, None, :] - c["mu"]) ** 2).sum(axis=-1), axis=-1)   # (N, rows)
+    hops = int(np.sum(np.any(near != near[:, :1], axis=1)))
+    print("margin %.3g  sensitivity %.3g  rejected %d/%d  chains changing component %d"
+          % (margin, sens, rejected, dE.size, hops))
+    assert margin >= 1e-6
+    assert sens <= 1e-11
+    assert frac <= 0.60 and (frac >= 0.05 or not reject_floor)
+    assert hops >= 1
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    c = recipe(name)
+    return c, oracle_run(c)
+
+
+def target_of(c):
+    from hmc_amd.target import MixtureTarget
+    return MixtureTarget(c["w"], c["mu"], c["var"])
+
+
+def sampler(c, rng="replay", **kw):
+    from hmc_amd.samplers import HMC_sampler
+    args = dict(Nchain=c["N"], Niter=c["Niter"], thin_rate=c["thin"], warm_up_num=c["wu"], cov_p=c["cov_p"],
+                sampler_type="Random", dt=c["dt"], L_low=c["Llo"], L_high=c["Lhi"], target=target_of(c), rng=rng)
+    args.update(kw)
+    h = HMC_sampler(c["D"], None, None, **args)
+    if rng == "replay":
+        h.set_random_replay(c["p0"], c["P"], c["L"], c["lnu"])
+    return h
+
+
+def assert_run_matches(h, ref):
+    """The bounds of the existing FAST-mode parity tests."""
+    assert h._acc == ref["accept_count"] and h._acc_wu == ref["accept_count_warm_up"]
+    assert h.n_leapfrog == ref["n_leapfrog"] and h.N_total_steps == ref["N_total_steps"]
+    np.testing.assert_allclose(h.q_chain, ref["q_chain"], rtol=1e-9, atol=1e-9)
+    np.testing.assert_allclose(h.E_chain[:, :, 0], ref["E_chain"], rtol=1e-10)
+    np.testing.assert_allclose(h.dE_chain[:, :, 0], ref["dE_chain"], rtol=1e-8, atol=1e-10)
+    assert h.accept_R == ref["accept_R"] and h.accept_R_warm_up == ref["accept_R_warm_up"]
+
+
+# ------------------------------------------------------------------------------------------ 1
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_primitives_vs_oracle(name):
+    """hmc_mix_energy / hmc_mix_leapfrog on 64 rows: 56 near the components and 8 at least 30 standard
+    deviations from every mean in every coordinate (exp underflows there without the max-shift)."""
+    c = recipe(name)
+    D, K = c["D"], c["K"]
+    rs = np.random.RandomState(1000 + c["seed"])
+    q = c["mu"][rs.randint(K, size=64)] + rs.standard_normal((64, D)) * np.sqrt(c["var"].max())
+    far = np.abs(c["mu"]).max() + 30.0 * np.sqrt(c["var"].max())
+    q[56:] = far * np.where(rs.random_sample((8, 1)) < 0.5, -1.0, 1.0) * (1.0 + 0.1 * rs.random_sample((8, D)))
+    p = rs.standard_normal((64, D)) * c["sd"]
+    h = sampler(c)
+    core = O.HMCCore(OracleMixture(c["w"], c["mu"], c["var"]), c["dt"], c["cov_p"])
+    E = h.E(q, p)
+    E_ref = np.array([core.E(q[i], p[i]) for i in range(64)])
+    assert np.all(np.isfinite(E)) and np.all(np.isfinite(E_ref))
+    np.testing.assert_allclose(E, E_ref, rtol=1e-10, atol=1e-12)
+    pn, qn = h.leap_frog(p, q)
+    ref = [core.leap_frog(p[i], q[i]) for i in range(64)]
+    np.testing.assert_allclose(pn, [r[0] for r in ref], rtol=1e-10, atol=1e-12)
+    np.testing.assert_allclose(qn, [r[1] for r in ref], rtol=1e-10, atol=1e-12)
+    e1, (p1, q1) = h.E(q[3], p[3]), h.leap_frog(p[3], q[3])          # single rows keep their shape
+    assert e1 == E[3] and np.array_equal(p1, pn[3]) and np.array_equal(q1, qn[3])
+
+
+# ------------------------------------------------------------------------------------------ 2
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_replay_parity(name):
+    c, ref = case(name)
+    check_input_conditions(c, ref, reject_floor=name != "E")
+    h = sampler(c, fp_mode="fast")
+    h.gen_sample(c["q_start"], verbose=False)
+    assert_run_matches(h, ref)
+    if name == "C":                                   # one arithmetic: fp_mode changes nothing
+        g = sampler(c, fp_mode="exact")
+        g.gen_sample(c["q_start"], verbose=False)
+        assert np.array_equal(g.q_chain, h.q_chain) and np.array_equal(g.E_chain, h.E_chain)
+        assert np.array_equal(g.dE_chain, h.dE_chain) and g._acc == h._acc and g.n_leapfrog == h.n_leapfrog
+
+
+# ------------------------------------------------------------------------------------------ 3
+def test_chain0_capture():
+    c, _ = case("A")
+    ref = oracle_run(c, n_save=8)
+    h = sampler(c)
+    h.gen_sample(c["q_start"], N_save_chain0=8, verbose=False)
+    assert_run_matches(h, ref)
+    assert np.array_equal(h.decision_chain[:, 0], ref["decision_chain"])
+    assert len(h.phi_q) == len(ref["phi_q"]) == 8
+    for a, b in zip(h.phi_q, ref["phi_q"]):
+        assert a.shape == b.shape
+        np.testing.assert_allclose(a, b, rtol=1e-9, atol=1e-9)
+
+
+# ------------------------------------------------------------------------------------------ 4
+def philox_streams(c, seed, chain0=0):
+    """The draws the kernel makes, regenerated on the host (tests/philox_host.py)."""
+    N, D, Niter = c["N"], c["D"], c["Niter"]
+    gcs = np.arange(chain0, chain0 + N, dtype=np.uint64)
+    npairs = (D + 1) // 2
+    z0, z1 = bm_pair(words(np.arange(npairs)[None, None, :], np.arange(Niter + 1)[None, :, None],
+                           gcs[:, None, None], seed))
+    z = np.stack([z0, z1], axis=3).reshape(N, Niter + 1, 2 * npairs)[:, :, :D] * c["sd"]
+    L, lnu = host_L_lnu(seed, gcs, Niter, c["Llo"], c["Lhi"])
+    return dict(c, p0=z[:, 0], P=z[:, 1:], L=L, lnu=lnu)
+
+
+def test_philox_parity():
+    # the Philox seed is an input like the recipe's: with 64 chains most seeds leave some chain more
+    # sensitive than condition 2 allows (1.6e-11 .. 4e-9 over seeds 1..24); 22 gives 6.0e-12
+    seed = 22
+    c = philox_streams(recipe("B", N=64, Niter=20), seed)
+    ref = oracle_run(c)
+    check_input_conditions(c, ref)
+    h = sampler(c, rng="philox", seed=seed, fp_mode="fast")
+    h.gen_sample(c["q_start"], verbose=False)
+    assert_run_matches(h, ref)
+
+
+# ------------------------------------------------------------------------------------------ 5
+def test_layout_and_launch_invariance():
+    c = recipe("C", N=96)
+
+    def run(q_start, **kw):
+        h = sampler(dict(c, N=len(q_start)), rng="philox", seed=5, **kw)
+        h.gen_sample(q_start, verbose=False)
+        return h
+
+    one = run(c["q_start"])
+    split = run(c["q_start"], iters_per_launch=7)
+    for a in ("q_chain", "E_chain", "dE_chain", "_acc", "_acc_wu", "n_leapfrog", "N_total_steps"):
+        assert np.array_equal(getattr(one, a), getattr(split, a)), a
+    lo, hi = run(c["q_start"][:48], chain_offset=0), run(c["q_start"][48:], chain_offset=48)
+    for a in ("q_chain", "E_chain", "dE_chain"):
+        assert np.array_equal(getattr(one, a), np.concatenate([getattr(lo, a), getattr(hi, a)])), a
+    for a in ("_acc", "_acc_wu", "n_leapfrog"):
+        assert getattr(one, a) == getattr(lo, a) + getattr(hi, a), a
+
+
+# ------------------------------------------------------------------------------------------ 6
+def test_window_storage():
+    """Every row into a circular window of R rows over 5 launches of 8 iterations (bench.py's storage
+    path): the window holds the last R rows of a stored run, bitwise."""
+    from hmc_amd.engine import MixtureEngine
+    c = recipe("C", N=24)
+    S, launches, R = 8, 5, 8
+    Niter, wu = S * launches, S + 1
+
+    def engine(store):
+        return MixtureEngine(target_of(c), c["N"], Niter, wu, 1, 5, 20, c["dt"], rng="philox", seed=11,
+                             store_chain=store)
+
+    full = engine(True)
+    full.init(c["q_start"])
+    full.run(1, Niter + 1)
+    eng = engine(False)
+    win = torch.zeros((c["N"], R, c["D"]), dtype=torch.float64, device=eng.device)
+    eng.set_chain_window(win, 0)
+    eng.init(c["q_start"])
+    for k in range(launches):
+        eng.run(1 + k * S, 1 + (k + 1) * S)
+    torch.cuda.synchronize()
+    rows = full.q_chain.shape[1]
+    assert rows % R == 0 and rows > R
+    assert torch.equal(win, full.q_chain[:, rows - R:])
+    assert torch.equal(eng.E_chain, full.E_chain) and torch.equal(eng.q, full.q)
+    assert np.array_equal(eng.read_counters(), full.read_counters())
+
+
+# ------------------------------------------------------------------------------------------ 7
+def test_streaming_diagnostics_match_stored_chain():
+    c = recipe("B", N=8, Niter=120)
+    c = dict(c, wu=20, thin=1)
+    out = []
+    for store in (True, False):
+        h = sampler(c, rng="philox", seed=21, store_chain=store)
+        h.gen_sample(c["q_start"], verbose=False)
+        h.compute_convergence_stats()
+        out.append(h)
+    full, st = out
+    assert st.q_chain is None and st.stream_info["truncated_dims"] == 0
+    assert st._acc == full._acc and st.n_leapfrog == full.n_leapfrog
+    np.testing.assert_allclose(st.R_q, full.R_q, rtol=1e-10)           # tests/test_gpu_exact_ess.py's bounds
+    np.testing.assert_allclose(st.n_eff_q, full.n_eff_q, rtol=1e-8)
+
+
+# ------------------------------------------------------------------------------------------ 8
+def test_stationarity():
+    """16,384 chains start at exact draws of the mixture; HMC leaves it invariant, so the final rows
+    are iid draws of it and every bound below is 5 standard errors of an exactly known moment."""
+    from hmc_amd.samplers import HMC_sampler
+    from hmc_amd.target import MixtureTarget
+    N, Niter = 16384, 30
+    w, mu = np.array([0.3, 0.7]), np.array([[-1.5, 0.0, 0.0], [1.5, 0.0, 0.0]])
+    t = MixtureTarget(w, mu, np.ones((2, 3)))
+    rs = np.random.RandomState(2024)
+    q_start = mu[rs.choice(2, size=N, p=w)] + rs.standard_normal((N, 3))
+    h = HMC_sampler(3, None, None, Nchain=N, Niter=Niter, sampler_type="Random", L_low=5,
+                    L_high=20, dt=0.3, target=t, rng="philox", seed=9)
+    h.gen_sample(q_start, verbose=False)
+    assert h.accept_R > 0
+    x = h.q_chain[:, -1, :]
+    assert not np.array_equal(x, q_start)
+    p_neg = float(np.sum(w * norm.cdf(-mu[:, 0])))
+    assert abs(np.mean(x[:, 0] < 0) - p_neg) <= 5 * np.sqrt(p_neg * (1 - p_neg) / N)
+    m, v = t.mean(), t.var()
+    assert np.all(np.abs(x.mean(axis=0) - m) <= 5 * np.sqrt(v / N))
+    delta = mu - m                                                     # component means about the mixture mean
+    mu4 = np.sum(w[:, None] * (delta ** 4 + 6 * delta ** 2 + 3.0), axis=0)   # unit variances
+    se_var = np.sqrt((mu4 - v ** 2 * (N - 3) / (N - 1)) / N)
+    assert np.all(np.abs(x.var(axis=0, ddof=1) - v) <= 5 * se_var)
+
+
+# ------------------------------------------------------------------------------------------ 9
+def test_non_finite_chain_is_rejected_and_isolated():
+    c = recipe("F")
+    bad = np.full((1, c["D"]), 1e200)
+    runs = []
+    for qs in (c["q_start"], np.concatenate([c["q_start"], bad])):
+        h = sampler(dict(c, N=len(qs)), rng="philox", seed=3)
+        h.gen_sample(qs, verbose=False)
+        runs.append(h)
+    ok, mixed = runs
+    assert np.array_equal(mixed.q_chain[:4], ok.q_chain) and np.array_equal(mixed.E_chain[:4], ok.E_chain)
+    assert np.all(mixed.q_chain[4] == 1e200)
+    assert (mixed._acc, mixed._acc_wu) == (ok._acc, ok._acc_wu)        # every proposal of the bad chain rejected
+    assert not np.any(np.isfinite(mixed.E_chain[4]))
+
+
+# ------------------------------------------------------------------------------------------ 10
+def test_refusals_and_mvn_unchanged():
+    from hmc_amd.samplers import HMC_sampler
+    from hmc_amd.target import MixtureTarget, MVNTarget
+    c = recipe("A")
+    t = target_of(c)
+    kw = dict(Nchain=2, Niter=10, dt=0.1, target=t)
+    with pytest.raises(NotImplementedError):
+        HMC_sampler(2, None, None, sampler_type="NUTS", d_max=5, **kw)
+    with pytest.raises(NotImplementedError):
+        HMC_sampler(2, None, None, sampler_type="Random", L_low=5, L_high=20,
+                    cov_p=np.array([[1.0, 0.2], [0.2, 1.0]]), **kw)
+    with pytest.raises(NotImplementedError):
+        HMC_sampler(513, None, None, sampler_type="Random", L_low=5, L_high=20, Nchain=2, Niter=10, dt=0.1,
+                    target=MixtureTarget([1.0], np.zeros((1, 513)), np.ones((1, 513))))
+    with pytest.raises(NotImplementedError):
+        HMC_sampler(2, None, None, sampler_type="Random", L_low=5, L_high=20, Nchain=2, Niter=10, dt=0.1,
+                    target=MixtureTarget(np.full(9, 1.0 / 9), np.zeros((9, 2)), np.ones((9, 2))))
+
+    def mvn():
+        D = 10
+        h = HMC_sampler(D, None, None, Nchain=16, Niter=20, sampler_type="Random", L_low=5, L_high=20, dt=0.1,
+                        target=MVNTarget(np.zeros(D), np.diag(np.linspace(0.5, 2.0, D))), rng="philox", seed=4,
+                        fp_mode="fast")
+        h.gen_sample(np.random.RandomState(0).standard_normal((16, D)), verbose=False)
+        return h
+
+    before = mvn()
+    m = sampler(c, rng="philox", seed=1)
+    m.gen_sample(c["q_start"], verbose=False)
+    after = mvn()
+    for a in ("q_chain", "E_chain", "dE_chain", "_acc", "n_leapfrog"):
+        assert np.array_equal(getattr(before, a), getattr(after, a)), a

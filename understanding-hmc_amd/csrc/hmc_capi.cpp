@@ -13,6 +13,7 @@
 
 #include "hmc.h"
 #include "hmc_internal.hpp"
+#include "hmc_mix.hpp"
 
 namespace {
 
@@ -527,6 +528,122 @@ hmc_status hmc_energy(const hmc_target* t, const hmc_kinetic* k, int64_t n, cons
   a.q = q;
   a.E = E_out;
   return hip_status(hmc::launch_energy_rows(a, (hipStream_t)stream), "hmc_energy");
+}
+
+// ---------------------------------------------------------------- Gaussian-mixture target
+namespace {
+
+hmc_status check_mixture(const hmc_mixture* m, const hmc_kinetic* k, const char* what) {
+  if (!m || !k) return fail(HMC_EINVAL, "%s: null mixture/kinetic", what);
+  if (m->D < 1) return fail(HMC_EINVAL, "%s: D must be >= 1", what);
+  if (m->K < 1) return fail(HMC_EINVAL, "%s: K must be >= 1", what);
+  if (!m->logw || !m->mu || !m->prec || !m->logdet_const)
+    return fail(HMC_EINVAL, "%s: mixture needs logw, mu, prec and logdet_const", what);
+  if (m->D > HMC_MIX_MAX_D) return fail(HMC_ENOTSUP, "%s: D=%d, the mixture kernels take D <= %d", what, m->D, HMC_MIX_MAX_D);
+  if (m->K > HMC_MIX_MAX_COMPONENTS)
+    return fail(HMC_ENOTSUP, "%s: K=%d, the mixture kernels take K <= %d", what, m->K, HMC_MIX_MAX_COMPONENTS);
+  if (k->minv_full || k->p_chol_t || k->kick)
+    return fail(HMC_ENOTSUP, "%s: a full cov_p is not supported for mixture targets (diagonal minv/p_scale only)", what);
+  return HMC_OK;
+}
+
+hmc_target mix_shape(const hmc_mixture* m) { return hmc_target{m->D, HMC_TARGET_DIAG, nullptr, nullptr, 0.0}; }
+
+hmc::MixArgs mix_args(const hmc_mixture* m, const hmc::RandArgs& a) {
+  hmc::MixArgs x{};
+  x.a = a;
+  x.Kc = m->K;
+  x.logw = m->logw;
+  x.mu = m->mu;
+  x.prec = m->prec;
+  x.ldc = m->logdet_const;
+  return x;
+}
+
+// Row-wise entries: the rows take the chains' place in the lane-group layout.
+hmc::MixArgs mix_row_args(const hmc_mixture* m, const hmc_kinetic* k, int64_t n, const hmc::Layout& lay) {
+  hmc::RandArgs a{};
+  a.n = n;
+  a.D = m->D;
+  a.npairs = lay.npairs;
+  a.lpc = lay.lpc;
+  a.cpw = lay.cpw;
+  a.dt = k->dt;
+  a.h = k->dt * 0.5;
+  a.minv = k->minv;
+  a.dtv = k->dt_vec;
+  return mix_args(m, a);
+}
+
+}  // namespace
+
+hmc_status hmc_mix_chain_init(const hmc_mixture* m, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
+                              const double* q_start, hmc_state* st, void* stream) {
+  if (hmc_status e = check_mixture(m, k, "hmc_mix_chain_init")) return e;
+  const hmc_target t = mix_shape(m);
+  if (hmc_status e = check_schedule(&t, k, s, false)) return e;
+  if (!st) return fail(HMC_EINVAL, "null state");
+  if (s->n_chains == 0) return HMC_OK;   // empty batch: zero-size buffers may be NULL
+  if (!st->q || !st->E_prev || !q_start) return fail(HMC_EINVAL, "null state/q_start");
+  const bool replay = s->rng_mode == HMC_RNG_REPLAY;
+  if (replay && (!r || !r->p0)) return fail(HMC_EINVAL, "replay mode needs p0");
+  const int L_lo = s->L_high > s->L_low ? s->L_low : 5, L_hi = s->L_high > s->L_low ? s->L_high : 20;
+  const hmc::Layout lay = hmc::mix_layout(m->D, L_lo, L_hi);
+  if (lay.K == 0) return fail(HMC_ENOTSUP, "D=%d too large for the mixture kernels", m->D);
+  hmc::RandArgs a = rand_args(&t, k, s, replay ? r : nullptr, st, lay);
+  a.qstart = q_start;
+  return hip_status(hmc::launch_mix_init(mix_args(m, a), lay, replay, (hipStream_t)stream), "hmc_mix_chain_init");
+}
+
+hmc_status hmc_mix_random_iters(const hmc_mixture* m, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
+                                hmc_state* st, void* stream) {
+  if (hmc_status e = check_mixture(m, k, "hmc_mix_random_iters")) return e;
+  const hmc_target t = mix_shape(m);
+  if (hmc_status e = check_schedule(&t, k, s, true)) return e;
+  if (!st) return fail(HMC_EINVAL, "null state");
+  if (hmc_status e = check_window(&t, s, st)) return e;
+  if (s->iter_begin < 1 || s->iter_end < s->iter_begin || s->iter_end > s->n_iter + 1)
+    return fail(HMC_EINVAL, "iteration range must satisfy 1 <= begin <= end <= Niter+1");
+  if (s->n_chains == 0) return HMC_OK;   // empty batch: zero-size buffers may be NULL
+  if (!st->q || !st->E_prev) return fail(HMC_EINVAL, "null state");
+  const bool replay = s->rng_mode == HMC_RNG_REPLAY;
+  if (replay && (!r || !r->p || !r->L || !r->lnu)) return fail(HMC_EINVAL, "replay mode needs p, L, lnu");
+  if (s->iter_end == s->iter_begin) return HMC_OK;
+  if (st->n_save > 0 && st->traj_q && st->traj_stride < s->L_high)
+    return fail(HMC_EINVAL, "traj_stride must be >= L_high");
+  const hmc::Layout lay = hmc::mix_layout(m->D, s->L_low, s->L_high);
+  if (lay.K == 0) return fail(HMC_ENOTSUP, "D=%d too large for the mixture kernels", m->D);
+  const hmc::RandArgs a = rand_args(&t, k, s, replay ? r : nullptr, st, lay);
+  return hip_status(hmc::launch_mix_iters(mix_args(m, a), lay, replay, (hipStream_t)stream), "hmc_mix_random_iters");
+}
+
+hmc_status hmc_mix_leapfrog(const hmc_mixture* m, const hmc_kinetic* k, int64_t n, const double* p, const double* q,
+                            double* p_out, double* q_out, void* stream) {
+  if (hmc_status e = check_mixture(m, k, "hmc_mix_leapfrog")) return e;
+  if (n < 0) return fail(HMC_EINVAL, "bad arguments");
+  if (n > 0 && (!p || !q || !p_out || !q_out)) return fail(HMC_EINVAL, "null row pointers");
+  if (p_out == p || q_out == q || p_out == q || q_out == p) return fail(HMC_EINVAL, "outputs alias inputs");
+  if (!std::isfinite(k->dt) && !k->dt_vec) return fail(HMC_EINVAL, "dt must be set (samplers.py:332)");
+  const hmc::Layout lay = hmc::mix_layout(m->D, 5, 20);
+  hmc::MixArgs x = mix_row_args(m, k, n, lay);
+  x.row_p = p;
+  x.row_q = q;
+  x.row_po = p_out;
+  x.row_qo = q_out;
+  return hip_status(hmc::launch_mix_rows(x, lay, true, (hipStream_t)stream), "hmc_mix_leapfrog");
+}
+
+hmc_status hmc_mix_energy(const hmc_mixture* m, const hmc_kinetic* k, int64_t n, const double* q, const double* p,
+                          double* E_out, void* stream) {
+  if (hmc_status e = check_mixture(m, k, "hmc_mix_energy")) return e;
+  if (n < 0) return fail(HMC_EINVAL, "bad arguments");
+  if (n > 0 && (!p || !q || !E_out)) return fail(HMC_EINVAL, "null row pointers");
+  const hmc::Layout lay = hmc::mix_layout(m->D, 5, 20);
+  hmc::MixArgs x = mix_row_args(m, k, n, lay);
+  x.row_p = p;
+  x.row_q = q;
+  x.row_E = E_out;
+  return hip_status(hmc::launch_mix_rows(x, lay, false, (hipStream_t)stream), "hmc_mix_energy");
 }
 
 hmc_status hmc_rng_normals(uint64_t seed, int64_t chain0, int64_t n, int32_t iteration, int32_t npairs, double* out,

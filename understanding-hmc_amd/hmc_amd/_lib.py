@@ -17,6 +17,7 @@ HMC_MODE_EXACT, HMC_MODE_FAST = 0, 1
  CNT_ENERGY_EVALS, CNT_HANDOFF_GIVEUP) = range(9)
 NCOUNTERS = 9
 COUNTER_SLOTS = 4096   # include/hmc.h HMC_COUNTER_SLOTS: counters buffer is [slots][NCOUNTERS]
+MIX_MAX_COMPONENTS, MIX_MAX_D = 8, 512   # include/hmc.h HMC_MIX_MAX_COMPONENTS, HMC_MIX_MAX_D
 
 c_dp = ctypes.c_void_p  # device pointers are passed as integers (torch data_ptr())
 
@@ -49,6 +50,12 @@ class State(ctypes.Structure):
                 ("counters", c_dp), ("traj_q", c_dp), ("traj_len", c_dp), ("decision", c_dp),
                 ("n_save", ctypes.c_int32), ("traj_stride", ctypes.c_int32),
                 ("qc_rows", ctypes.c_int64), ("qc_row0", ctypes.c_int64), ("order", c_dp)]
+
+
+class Mixture(ctypes.Structure):
+    """hmc_mixture: K Gaussians with diagonal covariances (device pointers)."""
+    _fields_ = [("D", ctypes.c_int32), ("K", ctypes.c_int32), ("logw", c_dp), ("mu", c_dp), ("prec", c_dp),
+                ("logdet_const", c_dp)]
 
 
 # Exported symbols (tests check every one of these is present; keep in sync with include/hmc.h)
@@ -86,6 +93,15 @@ SYMBOLS = {
                                     c_dp, c_dp, ctypes.c_int32, c_dp]),
     "hmc_energy": (ctypes.c_int, [ctypes.POINTER(Target), ctypes.POINTER(Kinetic), ctypes.c_int64, c_dp, c_dp,
                                   c_dp, c_dp]),
+    "hmc_mix_chain_init": (ctypes.c_int, [ctypes.POINTER(Mixture), ctypes.POINTER(Kinetic), ctypes.POINTER(Schedule),
+                                          ctypes.POINTER(Replay), c_dp, ctypes.POINTER(State), c_dp]),
+    "hmc_mix_random_iters": (ctypes.c_int, [ctypes.POINTER(Mixture), ctypes.POINTER(Kinetic),
+                                            ctypes.POINTER(Schedule), ctypes.POINTER(Replay), ctypes.POINTER(State),
+                                            c_dp]),
+    "hmc_mix_leapfrog": (ctypes.c_int, [ctypes.POINTER(Mixture), ctypes.POINTER(Kinetic), ctypes.c_int64, c_dp, c_dp,
+                                        c_dp, c_dp, c_dp]),
+    "hmc_mix_energy": (ctypes.c_int, [ctypes.POINTER(Mixture), ctypes.POINTER(Kinetic), ctypes.c_int64, c_dp, c_dp,
+                                      c_dp, c_dp]),
     "hmc_rng_normals": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                        ctypes.c_int32, c_dp, c_dp]),
     "hmc_philox": (ctypes.c_int, [ctypes.c_uint32] * 6 + [ctypes.c_int64, c_dp, c_dp]),

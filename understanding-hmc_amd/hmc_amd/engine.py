@@ -33,7 +33,34 @@ class RandomEngine:
         self.chain_offset = int(chain_offset)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         dev = self.device
-        # ---- target / kinetic descriptors (kept alive on the object)
+        kind = self._descriptors(target, cov_p, dt, dense)
+        # ---- state and outputs
+        N, Lc = self.N, self.L_chain
+        self.q = torch.zeros((N, D), dtype=torch.float64, device=dev)
+        self.E_prev = torch.zeros(N, dtype=torch.float64, device=dev)
+        self.q_chain = torch.zeros((N, Lc, D), dtype=torch.float64, device=dev) if store_chain else None
+        self.E_chain = torch.zeros((N, Lc), dtype=torch.float64, device=dev) if store_energy else None
+        self.dE_chain = torch.zeros((N, Lc), dtype=torch.float64, device=dev) if store_energy else None
+        self.counters = torch.zeros((H.COUNTER_SLOTS, H.NCOUNTERS), dtype=torch.int64, device=dev)
+        self.n_save = int(n_save)
+        if self.n_save:
+            self.traj_stride = max(self.L_high, 1)
+            self.traj = torch.zeros((self.n_save, self.traj_stride, 2), dtype=torch.float64, device=dev)
+            self.traj_len = torch.zeros(self.n_save, dtype=torch.int32, device=dev)
+            self.decision = torch.zeros(self.n_save, dtype=torch.int32, device=dev)
+        else:
+            self.traj_stride, self.traj, self.traj_len, self.decision = 0, None, None, None
+        self.S = H.State(H.ptr(self.q), H.ptr(self.E_prev), H.ptr(self.q_chain), H.ptr(self.E_chain),
+                         H.ptr(self.dE_chain), H.ptr(self.counters), H.ptr(self.traj), H.ptr(self.traj_len),
+                         H.ptr(self.decision), self.n_save, self.traj_stride)
+        self._alloc_workspace(kind, order_tiles, random_ws)
+        self._replay = None
+        self._streams = []
+
+    def _descriptors(self, target, cov_p, dt, dense):
+        """Target / kinetic descriptors self.T, self.K (their device arrays kept alive on the
+        object); returns the target kind."""
+        D, dev = self.D, self.device
         cov_p = np.diag(np.ones(D)) if cov_p is None else np.asarray(cov_p, dtype=np.float64)
         self.cov_p = cov_p
         full_mass = bool(np.any(cov_p - np.diag(np.diag(cov_p))))   # Q3 with a full cov_p
@@ -68,25 +95,10 @@ class RandomEngine:
         self.T = H.Target(D, kind, H.ptr(self._q0), H.ptr(self._prec), target.logdet_const)
         self.K = H.Kinetic(H.ptr(self._minv), H.ptr(self._pscale), H.ptr(self._dtv), dts, H.ptr(self._minv_full),
                            H.ptr(self._chol_t), H.ptr(self._kick))
-        # ---- state and outputs
-        N, Lc = self.N, self.L_chain
-        self.q = torch.zeros((N, D), dtype=torch.float64, device=dev)
-        self.E_prev = torch.zeros(N, dtype=torch.float64, device=dev)
-        self.q_chain = torch.zeros((N, Lc, D), dtype=torch.float64, device=dev) if store_chain else None
-        self.E_chain = torch.zeros((N, Lc), dtype=torch.float64, device=dev) if store_energy else None
-        self.dE_chain = torch.zeros((N, Lc), dtype=torch.float64, device=dev) if store_energy else None
-        self.counters = torch.zeros((H.COUNTER_SLOTS, H.NCOUNTERS), dtype=torch.int64, device=dev)
-        self.n_save = int(n_save)
-        if self.n_save:
-            self.traj_stride = max(self.L_high, 1)
-            self.traj = torch.zeros((self.n_save, self.traj_stride, 2), dtype=torch.float64, device=dev)
-            self.traj_len = torch.zeros(self.n_save, dtype=torch.int32, device=dev)
-            self.decision = torch.zeros(self.n_save, dtype=torch.int32, device=dev)
-        else:
-            self.traj_stride, self.traj, self.traj_len, self.decision = 0, None, None, None
-        self.S = H.State(H.ptr(self.q), H.ptr(self.E_prev), H.ptr(self.q_chain), H.ptr(self.E_chain),
-                         H.ptr(self.dE_chain), H.ptr(self.counters), H.ptr(self.traj), H.ptr(self.traj_len),
-                         H.ptr(self.decision), self.n_save, self.traj_stride)
+        return kind
+
+    def _alloc_workspace(self, kind, order_tiles, random_ws):
+        D = self.D
         # dense targets: scratch for L-ordered MFMA tiles (chains sorted by trajectory length
         # every iteration; same results, no lane idling through a longer trajectory).  The large-D
         # path (dense D > 128, diagonal D > 2048) keeps its chain state there: always allocated (a
@@ -100,11 +112,9 @@ class RandomEngine:
             nbytes = L_.hmc_random_workspace_size(self.T, self.N)
         else:
             nbytes = 0
-        self._order = torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=dev) if nbytes > 0 else None
+        self._order = torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=self.device) if nbytes > 0 else None
         self._order_bytes = self._order.numel() * 4 if self._order is not None else 0
         self.S.order = H.ptr(self._order)
-        self._replay = None
-        self._streams = []
 
     def set_chain_window(self, window, row0):
         """Store q_chain rows [row0, row0 + window.shape[1]) into `window` (N, W, D) instead of a
@@ -221,12 +231,14 @@ class RandomEngine:
         self.S.qc_row0 = 0
 
     # ---------------------------------------------------------------- checkpoint / resume
+    def _target_arrays(self):
+        return (self.t.q0, self.t.prec, np.float64(self.t.logdet_const))
+
     def _meta(self):
         """Everything that decides the chain's next values: a checkpoint restores only into an
         engine with the same schedule, step size, mass matrix and target."""
-        t = self.t
         h = hashlib.sha256()
-        for a in (t.q0, t.prec, np.float64(t.logdet_const)):
+        for a in self._target_arrays():
             h.update(np.ascontiguousarray(a, dtype=np.float64).tobytes())
         return dict(kind=type(self).__name__, N=self.N, D=self.D, n_iter=self.n_iter, warm_up=self.warm_up,
                     thin=self.thin, L_chain=self.L_chain, L_low=self.L_low, L_high=self.L_high, seed=self.seed,
@@ -302,6 +314,72 @@ class RandomEngine:
 
     def read_counters(self):
         return self.counters.cpu().numpy().astype(np.int64).sum(axis=0)
+
+
+class MixtureEngine(RandomEngine):
+    """Chain batch of the Random-trajectory sampler on a MixtureTarget (hmc_mix_chain_init /
+    hmc_mix_random_iters, csrc/hmc_mix.hip): RandomEngine's surface, state and outputs, with the
+    mixture descriptor in place of the MVN one.  Diagonal cov_p only, D <= 512, K <= 8; `fp_mode`
+    is accepted and changes nothing (one arithmetic: exp / log cannot be bit-identical to NumPy's)."""
+
+    def __init__(self, target, n_chains, n_iter, warm_up, thin, L_low, L_high, dt, cov_p=None, rng="philox",
+                 seed=0, fp_mode="fast", chain_offset=0, store_chain=True, store_energy=True, n_save=0,
+                 device=None):
+        super().__init__(target, n_chains, n_iter, warm_up, thin, L_low, L_high, dt, cov_p=cov_p, rng=rng, seed=seed,
+                         fp_mode=fp_mode, chain_offset=chain_offset, store_chain=store_chain,
+                         store_energy=store_energy, n_save=n_save, device=device)
+
+    @staticmethod
+    def check_supported(target, cov_p):
+        """NotImplementedError, before anything touches the device, for what the kernels do not take."""
+        if target.D > H.MIX_MAX_D or target.K > H.MIX_MAX_COMPONENTS:
+            raise NotImplementedError("mixture kernels: D=%d, K=%d (D <= %d, K <= %d)"
+                                      % (target.D, target.K, H.MIX_MAX_D, H.MIX_MAX_COMPONENTS))
+        if cov_p is not None:
+            cov_p = np.asarray(cov_p, dtype=np.float64)
+            if np.any(cov_p - np.diag(np.diag(cov_p))):
+                raise NotImplementedError("mixture kernels: a full cov_p is not supported (diagonal only)")
+
+    def _descriptors(self, target, cov_p, dt, dense):
+        self.check_supported(target, cov_p)
+        D, dev = self.D, self.device
+        cov_p = np.diag(np.ones(D)) if cov_p is None else np.asarray(cov_p, dtype=np.float64)
+        self.cov_p = cov_p
+        self._mix = [_dev(a, dev) for a in (target.logw, target.mu, target.prec, target.logdet_const)]
+        minv = np.diag(np.linalg.inv(cov_p)).astype(np.float64)          # samplers.py:356
+        ident_mass = bool(np.all(np.diag(cov_p) == 1.0) and np.all(minv == 1.0))
+        self._minv = None if ident_mass else _dev(minv, dev)
+        self._pscale = None if ident_mass else _dev(np.sqrt(np.diag(cov_p)), dev)
+        self._minv_full = None
+        dt = np.asarray(dt, dtype=np.float64)
+        self.dt = dt
+        if dt.ndim == 0:
+            self._dtv, dts = None, float(dt)
+        else:
+            assert dt.size == D
+            self._dtv, dts = _dev(dt.reshape(-1), dev), 0.0
+        self.T = H.Mixture(D, target.K, *[H.ptr(x) for x in self._mix])
+        self.K = H.Kinetic(H.ptr(self._minv), H.ptr(self._pscale), H.ptr(self._dtv), dts, None, None, None)
+        return None
+
+    def _alloc_workspace(self, kind, order_tiles, random_ws):
+        self._order, self._order_bytes = None, 0        # hmc_state.order is ignored by the mixture calls
+
+    def _target_arrays(self):
+        t = self.t
+        return (t.logw, t.mu, t.prec, t.logdet_const)
+
+    def init(self, q_start):
+        qs = q_start if isinstance(q_start, torch.Tensor) else _dev(np.asarray(q_start).reshape(self.N, self.D),
+                                                                    self.device)
+        self._qs = qs.to(self.device, torch.float64).contiguous()
+        H.check(H.lib().hmc_mix_chain_init(self.T, self.K, self.schedule(1, 1), self._replay, H.ptr(self._qs), self.S,
+                                           self.stream()), "hmc_mix_chain_init")
+
+    def run(self, it0, it1):
+        """Iterations [it0, it1) of every chain in ONE fused kernel launch."""
+        H.check(H.lib().hmc_mix_random_iters(self.T, self.K, self.schedule(it0, it1), self._replay, self.S,
+                                             self.stream()), "hmc_mix_random_iters")
 
 
 class NutsEngine(RandomEngine):

@@ -25,8 +25,8 @@ import torch
 
 from . import _lib as H
 from .diagnostics import StreamingDiagnostics
-from .engine import NutsEngine, RandomEngine
-from .target import MVNTarget, probe_closures  # noqa: F401
+from .engine import MixtureEngine, NutsEngine, RandomEngine
+from .target import MixtureTarget, MVNTarget, probe_closures  # noqa: F401
 from . import utils as U
 
 
@@ -76,10 +76,14 @@ class sampler(object):
 
 
 class HMC_sampler(sampler):
-    """HMC sampler for a multivariate-normal target on MI355X (samplers.py:297-924).
+    """HMC sampler for a multivariate-normal (or Gaussian-mixture) target on MI355X (samplers.py:297-924).
 
     Extra optional kwargs (all new; defaults keep the reference behaviour):
-      target   : MVNTarget; if None, V/dVdq are affine-probed (target.probe_closures)
+      target   : MVNTarget; if None, V/dVdq are affine-probed (target.probe_closures).  Or a
+                 MixtureTarget (K Gaussians with diagonal covariances; sampler_type="Random", a
+                 diagonal cov_p, D <= 512, K <= 8: anything else raises NotImplementedError here,
+                 before any launch; fp_mode changes nothing for it).  With a target, V / dVdq may
+                 be None: they are set to the target's host methods
       rng      : "replay" | "philox"
       seed     : Philox key (rng="philox")
       fp_mode  : "exact" (reference rounding, no FMA) | "fast" (FMA-contracted integrator)
@@ -141,6 +145,17 @@ class HMC_sampler(sampler):
         self.chain_offset = int(chain_offset)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self._target = target
+        if target is not None:
+            if self.V is None:
+                self.V = target.V
+            if self.dVdq is None:
+                self.dVdq = target.dVdq
+        self._mixture = isinstance(target, MixtureTarget)
+        if self._mixture:
+            assert target.D == self.D
+            if self.sampler_type == "NUTS":
+                raise NotImplementedError("NUTS on a mixture target is not supported (sampler_type='Random')")
+            MixtureEngine.check_supported(target, self.cov_p)
         self.n_leapfrog = 0
         self.q_chain_device = None
 
@@ -149,6 +164,24 @@ class HMC_sampler(sampler):
         if self._target is None:
             self._target = probe_closures(self.D, self.V, self.dVdq)
         return self._target
+
+    def _mix_descriptors(self):
+        """hmc_mixture + hmc_kinetic of a MixtureTarget (diagonal cov_p) for the row-wise calls."""
+        t, dev = self._target, self.device
+        cov_p = np.asarray(self.cov_p, dtype=np.float64)
+        keep = [_dev_tensor(a, dev) for a in (t.logw, t.mu, t.prec, t.logdet_const)]
+        M = H.Mixture(self.D, t.K, *[H.ptr(x) for x in keep])
+        minv_d = np.diag(self.inv_cov_p).astype(np.float64)
+        ident_mass = np.all(np.diag(cov_p) == 1.0) and np.all(minv_d == 1.0)
+        minv = None if ident_mass else _dev_tensor(minv_d, dev)
+        dt = np.asarray(self.dt, dtype=np.float64)
+        if dt.ndim == 0:
+            dtv, dts = None, float(dt)
+        else:
+            assert dt.size == self.D
+            dtv, dts = _dev_tensor(dt.reshape(-1), dev), 0.0
+        keep += [minv, dtv]
+        return M, H.Kinetic(H.ptr(minv), None, H.ptr(dtv), dts, None, None, None), keep
 
     def _descriptors(self):
         t = self.target()
@@ -217,18 +250,26 @@ class HMC_sampler(sampler):
             lnu = np.log(U_)
         return p0, P, Ls, lnu
 
+    def set_random_replay(self, p0, P, Ls, lnu):
+        """Explicit draw streams for rng="replay" with the Random sampler: p0 (Nchain, D), p (Nchain,
+        Niter, D), L (Nchain, Niter), log u (Nchain, Niter), used instead of drawing them from the
+        global np.random (RandomEngine.set_replay)."""
+        self._random_replay = (np.asarray(p0, np.float64), np.asarray(P, np.float64), np.asarray(Ls),
+                               np.asarray(lnu, np.float64))
+
     def gen_sample_random(self, q_start, N_save_chain0, verbose):
         """samplers.py:387-491 on the GPU (fused kernel hmc_random_iters via RandomEngine)."""
         q_start = np.asarray(q_start, dtype=np.float64)
         assert q_start.shape[0] == self.Nchain                                    # :396
         torch.cuda.set_device(self.device)
         n_save = int(N_save_chain0) if N_save_chain0 > 0 else 0
-        eng = RandomEngine(self.target(), self.Nchain, self.Niter, self.warm_up_num, self.thin_rate, self.L_low,
-                           self.L_high, self.dt, cov_p=self.cov_p, rng=self.rng, seed=self.seed,
-                           fp_mode=self.fp_mode, chain_offset=self.chain_offset, store_chain=self.store_chain,
-                           n_save=n_save, device=self.device)
+        engine = MixtureEngine if self._mixture else RandomEngine       # hmc_mix.hip / the MVN kernels
+        eng = engine(self.target(), self.Nchain, self.Niter, self.warm_up_num, self.thin_rate, self.L_low,
+                     self.L_high, self.dt, cov_p=self.cov_p, rng=self.rng, seed=self.seed,
+                     fp_mode=self.fp_mode, chain_offset=self.chain_offset, store_chain=self.store_chain,
+                     n_save=n_save, device=self.device)
         if self.rng == "replay":
-            eng.set_replay(*self._replay_streams_random())
+            eng.set_replay(*(getattr(self, "_random_replay", None) or self._replay_streams_random()))
         t0 = time.time()
         eng.init(q_start.reshape(self.Nchain, self.D))
         self._run(eng)
@@ -389,14 +430,18 @@ class HMC_sampler(sampler):
         """samplers.py:831-839 for one (p, q) row or a batch of rows, on the GPU."""
         p = np.atleast_2d(np.asarray(p_old, dtype=np.float64))
         q = np.atleast_2d(np.asarray(q_old, dtype=np.float64))
-        T, K, keep = self._descriptors()
+        T, K, keep = self._mix_descriptors() if self._mixture else self._descriptors()
         dev = self.device
         pt, qt = _dev_tensor(p, dev), _dev_tensor(q, dev)
         po, qo = torch.empty_like(pt), torch.empty_like(qt)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        H.check(H.lib().hmc_leapfrog(T, K, p.shape[0], H.ptr(pt), H.ptr(qt), H.ptr(po), H.ptr(qo),
-                                     H.HMC_MODE_EXACT if self.fp_mode == "exact" else H.HMC_MODE_FAST,
-                                     stream), "hmc_leapfrog")
+        if self._mixture:
+            H.check(H.lib().hmc_mix_leapfrog(T, K, p.shape[0], H.ptr(pt), H.ptr(qt), H.ptr(po), H.ptr(qo), stream),
+                    "hmc_mix_leapfrog")
+        else:
+            H.check(H.lib().hmc_leapfrog(T, K, p.shape[0], H.ptr(pt), H.ptr(qt), H.ptr(po), H.ptr(qo),
+                                         H.HMC_MODE_EXACT if self.fp_mode == "exact" else H.HMC_MODE_FAST,
+                                         stream), "hmc_leapfrog")
         pn, qn = po.cpu().numpy(), qo.cpu().numpy()
         if np.ndim(p_old) == 1:
             return pn[0], qn[0]
@@ -406,12 +451,13 @@ class HMC_sampler(sampler):
         """samplers.py:819-823 (V of utils.py:218 + K of :817) for one row or a batch."""
         qq = np.atleast_2d(np.asarray(q, dtype=np.float64))
         pp = np.atleast_2d(np.asarray(p, dtype=np.float64))
-        T, K, keep = self._descriptors()
+        T, K, keep = self._mix_descriptors() if self._mixture else self._descriptors()
         dev = self.device
         qt, pt = _dev_tensor(qq, dev), _dev_tensor(pp, dev)
         Et = torch.empty(qq.shape[0], dtype=torch.float64, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        H.check(H.lib().hmc_energy(T, K, qq.shape[0], H.ptr(qt), H.ptr(pt), H.ptr(Et), stream), "hmc_energy")
+        energy = H.lib().hmc_mix_energy if self._mixture else H.lib().hmc_energy
+        H.check(energy(T, K, qq.shape[0], H.ptr(qt), H.ptr(pt), H.ptr(Et), stream), "hmc_energy")
         E = Et.cpu().numpy()
         return E[0] if np.ndim(q) == 1 else E
 

@@ -11,7 +11,11 @@ explicitly.  Two ways in:
     (dVdq(0) and dVdq(e_i) give P = inv(cov0) column by column and q0; V(q0)
     gives the constant), verified at random points before it is trusted.
     For q0 = 0 (every reference driver) the probe is exact to the bit.
-Targets that are not MVN are rejected (no CPU fallback exists in the product).
+Closures that are not MVN are rejected (no CPU fallback exists in the product).
+
+One target that is not MVN has kernels of its own: `MixtureTarget(weights, mus, variances)`,
+a mixture of K Gaussians with diagonal covariances (csrc/hmc_mix.hip), passed as
+HMC_sampler(D, None, None, ..., target=MixtureTarget(...), sampler_type="Random").
 """
 import numpy as np
 
@@ -50,6 +54,70 @@ class MVNTarget:
 
     def dVdq(self, q):
         return np.dot(self.prec, np.asarray(q, dtype=np.float64) - self.q0)
+
+
+class MixtureTarget:
+    """Mixture of K Gaussians with diagonal covariances: weights (K,), mus (K, D), variances (K, D).
+
+    V(q) = -log sum_k w_k N(q; mu_k, diag var_k).  The host V / dVdq below (logsumexp, NumPy) serve
+    HMC_sampler.V / .dVdq and the plots; the chains run in csrc/hmc_mix.hip from the device
+    descriptor's arrays logw, mu, prec = 1/var and logdet_const_k = D log(2 pi) + sum_d log var_kd.
+    `q0` is the mixture mean (what the MVN targets call q0: where start points and plots centre)."""
+
+    diagonal = True
+
+    def __init__(self, weights, mus, variances):
+        self.w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        self.mu = np.ascontiguousarray(mus, dtype=np.float64)
+        self.variances = np.ascontiguousarray(variances, dtype=np.float64)
+        K = self.w.size
+        if self.mu.ndim != 2 or self.mu.shape[0] != K or self.variances.shape != self.mu.shape or self.mu.shape[1] < 1:
+            raise AssertionError("MixtureTarget takes weights (K,), mus (K, D), variances (K, D)")
+        if not (np.all(self.w > 0) and abs(self.w.sum() - 1.0) <= 1e-12):
+            raise AssertionError("mixture weights must be positive and sum to 1 (within 1e-12)")
+        if not np.all(self.variances > 0):
+            raise AssertionError("mixture variances must be positive")
+        self.logw = np.log(self.w)
+        self.prec = 1.0 / self.variances
+        self.logdet_const = self.D * np.log(2 * np.pi) + np.sum(np.log(self.variances), axis=1)
+        self.q0 = self.mean()
+
+    @property
+    def D(self):
+        return self.mu.shape[1]
+
+    @property
+    def K(self):
+        return self.w.size
+
+    def _log_terms(self, q):
+        """l_k = log w_k + log N(q; mu_k, diag var_k) and x = q - mu, for q (..., D)."""
+        x = np.asarray(q, dtype=np.float64)[..., None, :] - self.mu
+        return self.logw - 0.5 * (self.logdet_const + np.sum(self.prec * x * x, axis=-1)), x
+
+    def V(self, q):
+        l, _ = self._log_terms(q)
+        M = np.max(l, axis=-1)
+        return -(M + np.log(np.sum(np.exp(l - M[..., None]), axis=-1)))
+
+    def dVdq(self, q):
+        l, x = self._log_terms(q)
+        e = np.exp(l - np.max(l, axis=-1, keepdims=True))
+        r = e / np.sum(e, axis=-1, keepdims=True)
+        return np.sum(r[..., None] * (self.prec * x), axis=-2)
+
+    def mean(self):
+        """E[q_d] = sum_k w_k mu_kd."""
+        return self.w @ self.mu
+
+    def var(self):
+        """Var[q_d] = sum_k w_k (var_kd + mu_kd^2) - mean_d^2."""
+        return self.w @ (self.variances + self.mu ** 2) - self.mean() ** 2
+
+    def sample(self, n, rng):
+        """n exact draws from a np.random.RandomState (start points, tests)."""
+        k = rng.choice(self.K, size=n, p=self.w)
+        return self.mu[k] + np.sqrt(self.variances[k]) * rng.standard_normal((n, self.D))
 
 
 def probe_closures(D, V, dVdq, n_check=4, rtol=1e-9, seed=12345):
