@@ -185,6 +185,19 @@ hmc_status hmc_random_iters_ws(const hmc_target* t, const hmc_kinetic* k, const 
  * kick/drift loops (every other case, EXACT mode included). */
 int32_t hmc_random_leapfrog_form(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s);
 
+/* Which layout hmc_random_iters picks for a diagonal target (host only, no device access):
+ * out[0] = K coordinate pairs per lane, out[1] = lanes per chain, out[2] = chains per wave,
+ * out[3] = 1 for the wave-per-chain kernels (hmc_wave.hip), 0 for the lane-group kernel.
+ * Only t->D, t->kind, s->L_low and s->L_high are read.  The lane-group kernel (D <= 64) takes 36
+ * layouts over all trajectory-length ranges: K = 1 on 1..32 lanes, K = 2 on 3, 7, 9, 11 or 12
+ * lanes, K = 5 on 1..5 lanes, K = 4 on 3 or 7 lanes and K = 8 on 3 lanes; the many-pairs-per-lane
+ * ones (K = 4, K = 8, K = 5 on 3..5 lanes) only when the trajectory length is constant
+ * (L_high = L_low + 1) or its range is narrow against its mean.  It never takes K = 16
+ * (tests/test_layout_query.py holds the table).
+ * HMC_EINVAL for null arguments, D < 1 or L_low >= L_high; HMC_ENOTSUP for dense targets, the
+ * large-D path, or no layout. */
+hmc_status hmc_random_layout(const hmc_target* t, const hmc_schedule* s, int32_t out[4]);
+
 /* Record the size of a scratch buffer (hmc_state.order or a NUTS workspace) for the unsized entry
  * points: a later call that would need more than `bytes` returns HMC_EINVAL instead of writing past
  * the end.  bytes = 0 forgets the buffer; a record stays until the pointer is registered again, so

@@ -10,7 +10,8 @@ that no test leans on the GPU's own generator for its expected values.
     table-driven Box-Muller of hmc_device.hpp::normal_pair_tab, restated below with NumPy
     (1024-entry (cos, sin) and (1/c, -log 1/c) tables, the same bucket indices and series);
     iteration 0 (the initial momentum, samplers.py:415) uses hmc_device.hpp::normal_pair,
-    i.e. plain Box-Muller on the same 52-bit uniforms.
+    i.e. plain Box-Muller on the same 52-bit uniforms.  The lane-group kernels (D <= 64 and the
+    mixture target) use normal_pair at every iteration (group_momenta).
   * Trajectory length (samplers.py:441) and MH log-uniform (:461): block (0x80000000,
     iteration, chain): L = L_low + (x * (L_high - L_low)) >> 32, u = u53(z, w).
 The kernels' elementary functions are ~1 ulp; NumPy's are correctly rounded to ~0.5 ulp, so the
@@ -116,6 +117,19 @@ def table_normals(seed, chain0, n, it, npairs):
     gcs = np.arange(chain0, chain0 + n, dtype=np.uint64)
     z0, z1 = table_pair(words(np.arange(npairs)[None, :], it, gcs[:, None], seed))
     return np.stack([z0, z1], axis=2).reshape(n, 2 * npairs)
+
+
+def group_momenta(seed, gcs, D, niter):
+    """Lane-group kernels (hmc_random.hip::draw_momentum, hmc_mix.hip): pair k of (chain, iteration
+    it) holds dims 2k, 2k+1 and is the plain Box-Muller of block (k, it, chain) at every iteration,
+    it = 0 being the initial draw.  gcs: global chain ids.  Returns unit-variance p0 (N, D) and
+    P (N, niter, D); a diagonal cov_p scales them by sqrt(diag cov_p)."""
+    gcs = np.asarray(gcs, dtype=np.uint64)
+    npairs = (D + 1) // 2
+    z0, z1 = bm_pair(words(np.arange(npairs)[None, None, :], np.arange(niter + 1)[None, :, None],
+                           gcs[:, None, None], seed))
+    z = np.stack([z0, z1], axis=3).reshape(gcs.size, niter + 1, 2 * npairs)[:, :, :D]
+    return z[:, 0], z[:, 1:]
 
 
 def wave_momenta(seed, N, D, niter, chain0=0, normals=table_normals):

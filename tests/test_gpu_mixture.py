@@ -19,7 +19,7 @@ import torch
 from scipy.stats import norm
 
 from oracle import hmc_oracle as O
-from philox_host import bm_pair, host_L_lnu, words
+from philox_host import group_momenta, host_L_lnu
 
 pytestmark = pytest.mark.gpu
 
@@ -216,12 +216,9 @@ def philox_streams(c, seed, chain0=0):
     """The draws the kernel makes, regenerated on the host (tests/philox_host.py)."""
     N, D, Niter = c["N"], c["D"], c["Niter"]
     gcs = np.arange(chain0, chain0 + N, dtype=np.uint64)
-    npairs = (D + 1) // 2
-    z0, z1 = bm_pair(words(np.arange(npairs)[None, None, :], np.arange(Niter + 1)[None, :, None],
-                           gcs[:, None, None], seed))
-    z = np.stack([z0, z1], axis=3).reshape(N, Niter + 1, 2 * npairs)[:, :, :D] * c["sd"]
+    p0, P = group_momenta(seed, gcs, D, Niter)
     L, lnu = host_L_lnu(seed, gcs, Niter, c["Llo"], c["Lhi"])
-    return dict(c, p0=z[:, 0], P=z[:, 1:], L=L, lnu=lnu)
+    return dict(c, p0=p0 * c["sd"], P=P * c["sd"], L=L, lnu=lnu)
 
 
 def test_philox_parity():

@@ -350,6 +350,21 @@ int32_t hmc_random_leapfrog_form(const hmc_target* t, const hmc_kinetic* k, cons
   return hmc::leapfrog_three_term(a, lay, s->fp_mode == HMC_MODE_EXACT, general_diag(t, k)) ? 1 : 0;
 }
 
+hmc_status hmc_random_layout(const hmc_target* t, const hmc_schedule* s, int32_t out[4]) {
+  if (!t || !s || !out) return fail(HMC_EINVAL, "hmc_random_layout: null target/schedule/out");
+  if (t->D < 1) return fail(HMC_EINVAL, "D must be >= 1");
+  if (s->L_high <= s->L_low) return fail(HMC_EINVAL, "L_low must be < L_high (randint)");
+  if (t->kind == HMC_TARGET_DENSE) return fail(HMC_ENOTSUP, "hmc_random_layout: dense targets have no such layout");
+  if (hmc::big_path(false, t->D)) return fail(HMC_ENOTSUP, "hmc_random_layout: D=%d runs the large-D path", t->D);
+  const hmc::Layout lay = hmc::choose_layout(t->D, s->L_low, s->L_high);
+  if (lay.K == 0) return fail(HMC_ENOTSUP, "D=%d too large for the diagonal kernels", t->D);
+  out[0] = lay.K;
+  out[1] = lay.lpc;
+  out[2] = lay.cpw;
+  out[3] = hmc::wave_layout(lay) ? 1 : 0;
+  return HMC_OK;
+}
+
 int64_t hmc_random_workspace_size_ex(const hmc_target* t, const hmc_kinetic* k, int64_t n_chains) {
   if (!t || n_chains < 0 || t->D < 1) return 0;
   const bool dense = t->kind == HMC_TARGET_DENSE;

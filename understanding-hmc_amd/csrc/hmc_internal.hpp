@@ -92,6 +92,7 @@ inline NutsKernel nuts_kernel(int D) {
 }
 
 Layout choose_layout(int D, int L_low, int L_high);
+bool wave_layout(const Layout& lay);   // launch_random_iters takes the wave-per-chain kernels (hmc_wave.hip)
 
 hipError_t launch_random_init(const RandArgs& a, const Layout& lay, bool gen, bool replay, hipStream_t s);
 hipError_t launch_random_iters(const RandArgs& a, const Layout& lay, bool exact, bool gen, bool replay,

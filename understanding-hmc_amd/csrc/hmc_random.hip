@@ -445,7 +445,7 @@ hipError_t launch_random_init(const RandArgs& a, const Layout& lay, bool gen, bo
 }
 
 // The wave-per-chain kernels (hmc_wave.hip) serve this layout.
-static bool wave_layout(const Layout& lay) {
+bool wave_layout(const Layout& lay) {
 #ifdef HMC_DEBUG_HOOKS
   const char* kern = getenv("HMC_KERNEL");       // experiments: "group" forces the lane-group kernel
   const bool force_group = kern && kern[0] == 'g';

@@ -73,6 +73,8 @@ SYMBOLS = {
                                            ctypes.c_int64, c_dp]),
     "hmc_random_leapfrog_form": (ctypes.c_int32, [ctypes.POINTER(Target), ctypes.POINTER(Kinetic),
                                                   ctypes.POINTER(Schedule)]),
+    "hmc_random_layout": (ctypes.c_int, [ctypes.POINTER(Target), ctypes.POINTER(Schedule),
+                                         ctypes.POINTER(ctypes.c_int32 * 4)]),
     "hmc_workspace_register": (ctypes.c_int, [c_dp, ctypes.c_int64]),
     "hmc_stream_work_size": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
     "hmc_stream_accumulate": (ctypes.c_int, [c_dp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
@@ -159,6 +161,16 @@ def check(status, what=""):
     if status == HMC_ENOTSUP:
         raise NotImplementedError(text)
     raise HMCError(text)
+
+
+def random_layout(D, L_low, L_high):
+    """hmc_random_layout for a diagonal target (host only): (K pairs per lane, lanes per chain,
+    chains per wave, 1 for the wave-per-chain kernels / 0 for the lane-group kernel)."""
+    T = Target(D, HMC_TARGET_DIAG, None, None, 0.0)
+    S = Schedule(0, 0, 1, 0, 1, 2, L_low, L_high, 1, 1, HMC_RNG_PHILOX, HMC_MODE_FAST, 10, 0, 0)
+    out = (ctypes.c_int32 * 4)()
+    check(lib().hmc_random_layout(ctypes.byref(T), ctypes.byref(S), ctypes.byref(out)), "hmc_random_layout")
+    return tuple(out)
 
 
 def ptr(t):
