@@ -85,7 +85,21 @@ typedef struct hmc_kinetic {
    * Random and NUTS samplers (NUTS reads minv_full and kick; p_chol_t for Philox draws).  */
   const double* minv_full; /* [D*D] inv(cov_p), row-major (symmetric)                     */
   const double* p_chol_t;  /* [D*D] transpose of the lower Cholesky factor C of cov_p:
-                              Philox momentum p = C z, z ~ N(0, I)                        */
+                              Philox momentum p = C z, z ~ N(0, I), i.e. p_r = sum_k
+                              p_chol_t[k*D + r] z_k (passing C itself gives C^T z: the same
+                              law, other values).  Where z_d lives, per kernel family
+                              (block (slot, iteration, chain_lo, chain_hi), key = seed;
+                              iteration 0, the initial draw, plain Box-Muller, later ones
+                              the table transform; p_scale scales the same z_d):
+                                dense targets D <= 128 (Random and NUTS), NUTS at any D:
+                                  d = h + 4m (h < 4): slot h + 4(m - (m & 1)), half m & 1;
+                                diagonal targets at D > 64 (the wave-per-chain kernels),
+                                  Random with a dense target at D > 128, and iteration 0 of
+                                  every run at D > 128 (NUTS included): slot d / 2, half d & 1.
+                              Above D = 128 the full-cov_p NUTS stream is the lockstep
+                              kernel's (D <= 320): the same blocks as the per-chain kernel
+                              beyond, C z summed as a block GEMM
+                              (tests/test_gpu_philox_mass.py pins all of this).            */
   const double* kick;      /* [D*D] inv(cov_p) . prec, row-major: the kick matrix          */
 } hmc_kinetic;
 

@@ -291,6 +291,7 @@ def gen_sample_nuts(core, q_start, Nchain, Niter, warm_up, thin, d_max, draws, o
     n_total = 0
     n_lf = 0
     n_unstable = 0
+    n_dmax = 0
     for m in range(Nchain):
         q_chain[m, 0] = q_start[m]                                       # :548
         q_tmp = q_start[m]
@@ -319,6 +320,7 @@ def gen_sample_nuts(core, q_start, Nchain, Niter, warm_up, thin, d_max, draws, o
                 if d > d_max - 1:                                        # :596-598 (Q12)
                     if on_dmax == "raise":
                         raise AssertionError("Doubling number d exceeds d_max = %d" % d_max)
+                    n_dmax += 1
                     break
                 table[:] = -1                                            # :601
                 L_new = 2 ** d
@@ -405,7 +407,7 @@ def gen_sample_nuts(core, q_start, Nchain, Niter, warm_up, thin, d_max, draws, o
             if i >= warm_up:                                             # :790-791
                 q_chain[m, (i - warm_up) // thin] = q_tmp
     return dict(q_chain=q_chain, E_chain=E_chain, dE_chain=dE_chain, N_total_steps=n_total,
-                n_leapfrog=n_lf, n_unstable=n_unstable, accept_R=1.,
+                n_leapfrog=n_lf, n_unstable=n_unstable, n_dmax=n_dmax, accept_R=1.,
                 accept_R_warm_up=1. if warm_up > 0 else None)
 
 

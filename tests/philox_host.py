@@ -12,6 +12,11 @@ that no test leans on the GPU's own generator for its expected values.
     iteration 0 (the initial momentum, samplers.py:415) uses hmc_device.hpp::normal_pair,
     i.e. plain Box-Muller on the same 52-bit uniforms.  The lane-group kernels (D <= 64 and the
     mixture target) use normal_pair at every iteration (group_momenta).
+  * Dense-target kernels at D <= 128 and the NUTS kernels at every D: dim d = h + 4m reads slot
+    h + 4 (m - (m & 1)), half m & 1 (dense_momenta); above D = 128 the chains are initialised by
+    hmc_big.hip, whose iteration 0 is in the pair-k mapping (pair_p0).
+  * All helpers return unit normals z and take global chain ids; the caller applies the mass
+    matrix: z @ C.T with C = chol(cov_p), or z * sqrt(diag cov_p).
   * Trajectory length (samplers.py:441) and MH log-uniform (:461): block (0x80000000,
     iteration, chain): L = L_low + (x * (L_high - L_low)) >> 32, u = u53(z, w).
 The kernels' elementary functions are ~1 ulp; NumPy's are correctly rounded to ~0.5 ulp, so the
@@ -19,6 +24,8 @@ momenta agree to a few 1e-15 (checked against the C-ABI debug entry hmc_rng_norm
 tests/test_gpu_philox_parity.py), far inside the 1e-9 q tolerance of the parity tests.
 """
 import numpy as np
+
+from oracle.hmc_oracle import ReplayDraws
 
 KDRAW = 0x80000000
 M32 = np.uint64(0xFFFFFFFF)
@@ -132,12 +139,78 @@ def group_momenta(seed, gcs, D, niter):
     return z[:, 0], z[:, 1:]
 
 
+def pair_p0(seed, gcs, D):
+    """Iteration 0 of the pair-k mapping (dims 2k, 2k+1 in slot k): plain Box-Muller, (N, D).
+    hmc_wave.hip and hmc_big.hip; hmc_big.hip also initialises the NUTS chains above D = 128."""
+    gcs = np.asarray(gcs, dtype=np.uint64)
+    npairs = (D + 1) // 2
+    z0, z1 = bm_pair(words(np.arange(npairs)[None, :], 0, gcs[:, None], seed))
+    return np.stack([z0, z1], axis=2).reshape(gcs.size, 2 * npairs)[:, :D]
+
+
 def wave_momenta(seed, N, D, niter, chain0=0, normals=table_normals):
     """Diagonal kernels: pair k holds dims 2k, 2k+1 (slot k).  p0 (iteration 0) from normal_pair,
     iterations >= 1 from the table transform (`normals`: the host restatement by default)."""
     npairs = (D + 1) // 2
-    gcs = np.arange(chain0, chain0 + N, dtype=np.uint64)
-    z0, z1 = bm_pair(words(np.arange(npairs)[None, :], 0, gcs[:, None], seed))
-    p0 = np.stack([z0, z1], axis=2).reshape(N, 2 * npairs)[:, :D]
+    p0 = pair_p0(seed, np.arange(chain0, chain0 + N, dtype=np.uint64), D)
     P = np.stack([normals(seed, chain0, N, it, npairs)[:, :D] for it in range(1, niter + 1)], axis=1)
     return p0, P
+
+
+def dense_slot_index(D):
+    """Dense/NUTS kernels: dims h + 4m (h < 4), pairs (m, m+1) for even m in slot h + 4m:
+    dim d -> (slot, which of the pair)."""
+    d = np.arange(D)
+    h, m = d % 4, d // 4
+    return h + 4 * (m - (m & 1)), m & 1
+
+
+def dense_momenta(seed, gcs, D, niter, table=True, pair0=False):
+    """Dense-target and NUTS kernels: unit normals z of the global chains `gcs` in the h + 4m
+    mapping (dense_slot_index): p0 (N, D) of iteration 0 (plain Box-Muller) and P (N, niter, D) of
+    iterations 1..niter (the table transform; table=False: plain Box-Muller there too).
+    pair0: iteration 0 in the pair-k mapping instead (pair_p0): the NUTS kernels above D = 128,
+    whose chains hmc_big.hip initialises.  The caller applies the mass matrix: z @ C.T with
+    C = chol(cov_p), or z * sqrt(diag cov_p)."""
+    gcs = np.asarray(gcs, dtype=np.uint64)
+    slot, which = dense_slot_index(D)
+    pick = which[None, :] == 0
+    if pair0:
+        p0 = pair_p0(seed, gcs, D)
+    else:
+        z = bm_pair(words(slot[None, :], 0, gcs[:, None], seed))
+        p0 = np.where(pick, z[0], z[1])
+    P = np.empty((gcs.size, niter, D))
+    for it in range(1, niter + 1):
+        z = (table_pair if table else bm_pair)(words(slot[None, :], it, gcs[:, None], seed))
+        P[:, it - 1] = np.where(pick, z[0], z[1])
+    return p0, P
+
+
+class PhiloxNutsDraws(ReplayDraws):
+    """The NUTS kernels' Philox streams as an oracle draw source: momenta per iteration and the
+    k-th direction/uniform of an iteration from block (0x80000000 + k, iteration, chain),
+    chain = gcs[m] the global id of oracle chain m."""
+
+    def __init__(self, seed, p0, P, gcs):
+        super().__init__(p0, P)
+        self.seed = seed
+        self.gcs = np.asarray(gcs, dtype=np.uint64)
+        self.it = {}
+        self.k = {}
+
+    def p(self, m, i):
+        self.it[m], self.k[m] = i, 0
+        return super().p(m, i)
+
+    def _block(self, m):
+        w = words(KDRAW + self.k[m], self.it[m], self.gcs[m], self.seed)
+        self.k[m] += 1
+        return w
+
+    def direction(self, m):
+        return int(self._block(m)[0] & np.uint64(1))
+
+    def uniform(self, m):
+        w = self._block(m)
+        return float(u53(w[2], w[3]))

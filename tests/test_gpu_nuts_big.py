@@ -146,7 +146,7 @@ def test_nuts_large_D_full_cov_p_vs_oracle(D, fp_mode):
     """A full (non-diagonal) cov_p above D = 128 (samplers.py:352-356, :811-839 through
     gen_sample_NUTS): at D = 136 and 300 the lockstep kernel's block GEMMs (round 6: P x, the kick
     inv_cov_p . P x, and inv_cov_p p for K), at D = 330 the per-chain kernel's GEMVs, on replayed
-    draws vs the oracle; plus Philox determinism."""
+    draws vs the oracle; plus Philox determinism (all three D, both modes)."""
     import make_golden_shapes as S
     from hmc_amd import _lib as H
     from hmc_amd.engine import NutsEngine
@@ -173,19 +173,18 @@ def test_nuts_large_D_full_cov_p_vs_oracle(D, fp_mode):
     assert int(c[H.CNT_UNSTABLE]) == ref["n_unstable"]
     np.testing.assert_allclose(eng.q_chain.cpu().numpy(), ref["q_chain"], rtol=1e-9, atol=1e-9)
     np.testing.assert_allclose(eng.E_chain.cpu().numpy(), ref["E_chain"], rtol=1e-10, atol=1e-10)
-    if D != 136 or fp_mode != "fast":
-        return
-    # Philox (p = C z): finite and repeatable.  No stationarity check here: the reference's NUTS
-    # with a cov_p other than the identity (Q3 leapfrog, Q11 ratio) does not keep N(0, Sigma) --
-    # the oracle itself, on np.random draws at D = 8, 1,500 chains, 3 iterations, dt = 0.2: mean
-    # per-dim variance 1.38 (full cov_p), 1.30 (its diagonal), 1.05 (identity) -- and the replay
-    # parity above pins this kernel to the reference's behaviour instead.
+    # Philox (p = C z): finite and repeatable, at every D and mode.  The values are pinned by
+    # tests/test_gpu_philox_mass.py (host-regenerated draws through the oracle).  No stationarity
+    # check: the reference's NUTS with a cov_p other than the identity (Q3 leapfrog, Q11 ratio) does
+    # not keep N(0, Sigma) -- the oracle itself, on np.random draws at D = 8, 1,500 chains, 3
+    # iterations, dt = 0.2: mean per-dim variance 1.38 (full cov_p), 1.30 (its diagonal), 1.05
+    # (identity).
     N2 = 256
     qs = np.random.RandomState(4).standard_normal((N2, D)) @ np.linalg.cholesky(cov).T
 
     def run():
         e = NutsEngine(MVNTarget(np.zeros(D), cov), N2, 3, 1, 1, 8, 0.2, cov_p=cov_p, rng="philox", seed=6,
-                       on_dmax="break")
+                       fp_mode=fp_mode, on_dmax="break")
         e.init(qs)
         e.run(1, 4)
         torch.cuda.synchronize()

@@ -24,7 +24,7 @@ import pytest
 import torch
 
 from oracle import hmc_oracle as O
-from philox_host import KDRAW, bm_pair, host_L_lnu, table_normals, u53, wave_momenta, words
+from philox_host import PhiloxNutsDraws, dense_momenta, host_L_lnu, table_normals, wave_momenta
 
 pytestmark = pytest.mark.gpu
 
@@ -46,30 +46,6 @@ def test_table_normals_match_kernel(npairs, chain0, it):
     h = table_normals(seed, chain0, 96, it, npairs)
     assert np.all(np.isfinite(g))
     np.testing.assert_allclose(g, h, rtol=0, atol=1e-13)
-
-
-def dense_slot_index(D):
-    """Dense/NUTS kernels: dims h + 4m (h < 4), pairs (m, m+1) for even m in slot h + 4m:
-    dim d -> (slot, which of the pair)."""
-    d = np.arange(D)
-    h, m = d % 4, d // 4
-    return h + 4 * (m - (m & 1)), m & 1
-
-
-def dense_momenta(seed, N, D, niter, table=True):
-    slot, which = dense_slot_index(D)
-    gcs = np.arange(N, dtype=np.uint64)
-    z = bm_pair(words(slot[None, :], 0, gcs[:, None], seed))
-    p0 = np.where(which[None, :] == 0, z[0], z[1])
-    P = np.empty((N, niter, D))
-    for it in range(1, niter + 1):
-        if table:
-            g = table_normals(seed, 0, N, it, D)
-            P[:, it - 1] = g[:, 2 * slot + which]
-        else:
-            z = bm_pair(words(slot[None, :], it, gcs[:, None], seed))
-            P[:, it - 1] = np.where(which[None, :] == 0, z[0], z[1])
-    return p0, P
 
 
 class FastMVN(O.MVNTarget):
@@ -267,7 +243,7 @@ def test_dense_production_kernel_vs_oracle(fp_mode):
     h = HMC_sampler(D, None, None, Nchain=N, Niter=Niter, sampler_type="Random", L_low=5, L_high=20, dt=0.1,
                     warm_up_num=wu, target=MVNTarget(np.zeros(D), cov), rng="philox", seed=seed, fp_mode=fp_mode)
     h.gen_sample(q_start, verbose=False)
-    p0, P = dense_momenta(seed, N, D, Niter)
+    p0, P = dense_momenta(seed, np.arange(N), D, Niter)
     L, lnu = host_L_lnu(seed, np.arange(N, dtype=np.uint64), Niter, 5, 20)
     ref = O.gen_sample_random(O.HMCCore(FastMVN(np.zeros(D), cov), 0.1), q_start, N, Niter, wu, 1, 5, 20,
                               O.ReplayDraws(p0, P, L, lnu))
@@ -275,33 +251,6 @@ def test_dense_production_kernel_vs_oracle(fp_mode):
     assert h.n_leapfrog == ref["n_leapfrog"]
     np.testing.assert_allclose(h.q_chain, ref["q_chain"], rtol=1e-9, atol=1e-9)
     np.testing.assert_allclose(h.E_chain[:, 1:, 0], ref["E_chain"][:, 1:], rtol=1e-10)
-
-
-class PhiloxNutsDraws(O.ReplayDraws):
-    """The NUTS kernel's Philox streams as an oracle draw source: momenta per iteration and the
-    k-th direction/uniform of an iteration from block (0x80000000 + k, iteration, chain)."""
-
-    def __init__(self, seed, p0, P):
-        super().__init__(p0, P)
-        self.seed = seed
-        self.it = {}
-        self.k = {}
-
-    def p(self, m, i):
-        self.it[m], self.k[m] = i, 0
-        return super().p(m, i)
-
-    def _block(self, m):
-        w = words(KDRAW + self.k[m], self.it[m], m, self.seed)
-        self.k[m] += 1
-        return w
-
-    def direction(self, m):
-        return int(self._block(m)[0] & np.uint64(1))
-
-    def uniform(self, m):
-        w = self._block(m)
-        return float(u53(w[2], w[3]))
 
 
 @pytest.mark.parametrize("fp_mode", ["fast", "exact"])
@@ -317,9 +266,9 @@ def test_nuts_production_kernel_vs_oracle(fp_mode):
     h = HMC_sampler(D, None, None, Nchain=N, Niter=Niter, warm_up_num=wu, sampler_type="NUTS", dt=0.1, d_max=d_max,
                     target=MVNTarget(np.zeros(D), cov), rng="philox", seed=seed, fp_mode=fp_mode)
     h.gen_sample_NUTS(q_start, 0, False, on_dmax="break")
-    p0, P = dense_momenta(seed, N, D, Niter)
+    p0, P = dense_momenta(seed, np.arange(N), D, Niter)
     ref = O.gen_sample_nuts(O.HMCCore(FastMVN(np.zeros(D), cov), 0.1), q_start, N, Niter, wu, 1, d_max,
-                            PhiloxNutsDraws(seed, p0, P), on_dmax="break")
+                            PhiloxNutsDraws(seed, p0, P, np.arange(N)), on_dmax="break")
     assert h.n_leapfrog == ref["n_leapfrog"]
     assert h.n_unstable == ref["n_unstable"]
     np.testing.assert_allclose(h.q_chain, ref["q_chain"], rtol=1e-9, atol=1e-9)
