@@ -323,6 +323,53 @@ hmc_status hmc_mix_leapfrog(const hmc_mixture* m, const hmc_kinetic* k, int64_t 
 hmc_status hmc_mix_energy(const hmc_mixture* m, const hmc_kinetic* k, int64_t n, const double* q,
                           const double* p, double* E_out, void* stream);
 
+/* ---------------------------------------------------------------- logistic-regression target
+ * The posterior of regression coefficients q given a design matrix X (n, D), labels y in {0, 1}
+ * and an independent zero-mean normal prior: the first target defined by data, for the
+ * Random-trajectory sampler.  With z = X q (no normalising constants):
+ *   V(q)    = sum_j [ softplus(z_j) - y_j z_j ] + 0.5 sum_d prior_prec_d q_d^2
+ *   dV/dq   = X^T (sigma(z) - y) + prior_prec q
+ *   softplus(z) = max(z, 0) + log(1 + exp(-|z|)),  sigma(z) = 1/(1+t) for z >= 0, t/(1+t) otherwise,
+ *   t = exp(-|z|): forms that never overflow  (hmc_logit.hip: 16 chains per wave, both products
+ *   on the f64 matrix cores). */
+enum { HMC_LOGIT_MAX_D = 128, HMC_LOGIT_MAX_N = 1 << 20 };
+typedef struct hmc_logistic {
+  int32_t D, n;               /* 1 <= D <= HMC_LOGIT_MAX_D, 1 <= n <= HMC_LOGIT_MAX_N        */
+  int64_t ldx;                /* row stride of X in doubles, >= D                            */
+  const double* X;            /* [n][ldx] design matrix, row-major                           */
+  const double* y;            /* [n] labels, 0.0 or 1.0                                      */
+  const double* prior_prec;   /* [D] 1 / prior_var                                           */
+} hmc_logistic;               /* device pointers; 40 bytes: offsets 0, 4, 8, 16, 24, 32      */
+
+/* hmc_chain_init / hmc_random_iters for a logistic target, argument for argument the mixture
+ * entries above with hmc_logistic in place of hmc_mixture.  hmc_kinetic, hmc_schedule, hmc_replay
+ * and hmc_state mean exactly what they mean there: replay and Philox modes, chain_offset,
+ * iter_begin / iter_end, the circular window qc_rows / qc_row0, the n_save capture of global chain
+ * 0, the counters ACCEPT, ACCEPT_WU, LEAPFROG, LEAPFROG_SQ (sum of L^2) and OOB_REJECT.
+ * hmc_state.order is ignored.  schedule.fp_mode may be either value: there is one arithmetic (exp
+ * and log are ~1 ulp fp64, which cannot be bit-identical to NumPy's, so no EXACT form exists).
+ * Philox draws are the dense Random kernel's: the momentum of dim d = h + 4m (h < 4) of (chain,
+ * iteration it) is half m & 1 of the Box-Muller pair of block (h + 4 (m - (m & 1)), it, chain),
+ * plain Box-Muller at it = 0 (the initial draw) and the table transform afterwards, scaled by
+ * p_scale; (L, u) come from block (0x80000000, it, chain).  Results do not depend on which 16-chain
+ * tile column a chain occupies, on the launch split or on the number of GPUs.
+ * HMC_EINVAL: null X / y / prior_prec, D < 1, n < 1, ldx < D.  HMC_ENOTSUP: D > HMC_LOGIT_MAX_D,
+ * n > HMC_LOGIT_MAX_N, or a full cov_p (minv_full, p_chol_t or kick non-NULL); the diagonal minv,
+ * p_scale and dt_vec are supported.  Then the schedule's own checks; an empty batch returns HMC_OK. */
+hmc_status hmc_logit_chain_init(const hmc_logistic* m, const hmc_kinetic* k, const hmc_schedule* s,
+                                const hmc_replay* r /* NULL for Philox */, const double* q_start, hmc_state* st,
+                                void* stream);
+hmc_status hmc_logit_random_iters(const hmc_logistic* m, const hmc_kinetic* k, const hmc_schedule* s,
+                                  const hmc_replay* r /* NULL for Philox */, hmc_state* st, void* stream);
+
+/* Batched single leapfrog step and total energy of n rows on a logistic target (tiles of 16 rows
+ * through the same gradient as the chains): HMC_sampler.leap_frog, samplers.py:831-839, and E / K,
+ * :811-823. */
+hmc_status hmc_logit_leapfrog(const hmc_logistic* m, const hmc_kinetic* k, int64_t n, const double* p,
+                              const double* q, double* p_out, double* q_out, void* stream);
+hmc_status hmc_logit_energy(const hmc_logistic* m, const hmc_kinetic* k, int64_t n, const double* q,
+                            const double* p, double* E_out, void* stream);
+
 /* The standard normals the Philox mode draws for (chain, iteration): out[n][2*npairs].
  * Debug/verification entry (statistical tests of the in-kernel generator). */
 hmc_status hmc_rng_normals(uint64_t seed, int64_t chain0, int64_t n, int32_t iteration,

@@ -13,6 +13,7 @@
 
 #include "hmc.h"
 #include "hmc_internal.hpp"
+#include "hmc_logit.hpp"
 #include "hmc_mix.hpp"
 
 namespace {
@@ -659,6 +660,115 @@ hmc_status hmc_mix_energy(const hmc_mixture* m, const hmc_kinetic* k, int64_t n,
   x.row_q = q;
   x.row_E = E_out;
   return hip_status(hmc::launch_mix_rows(x, lay, false, (hipStream_t)stream), "hmc_mix_energy");
+}
+
+// ---------------------------------------------------------------- logistic-regression target
+namespace {
+
+hmc_status check_logistic(const hmc_logistic* m, const hmc_kinetic* k, const char* what) {
+  if (!m || !k) return fail(HMC_EINVAL, "%s: null logistic/kinetic", what);
+  if (m->D < 1) return fail(HMC_EINVAL, "%s: D must be >= 1", what);
+  if (m->n < 1) return fail(HMC_EINVAL, "%s: n must be >= 1", what);
+  if (!m->X || !m->y || !m->prior_prec) return fail(HMC_EINVAL, "%s: logistic target needs X, y and prior_prec", what);
+  if (m->ldx < m->D) return fail(HMC_EINVAL, "%s: ldx=%lld < D=%d", what, (long long)m->ldx, m->D);
+  if (m->D > HMC_LOGIT_MAX_D)
+    return fail(HMC_ENOTSUP, "%s: D=%d, the logistic kernels take D <= %d", what, m->D, HMC_LOGIT_MAX_D);
+  if (m->n > HMC_LOGIT_MAX_N)
+    return fail(HMC_ENOTSUP, "%s: n=%d, the logistic kernels take n <= %d", what, m->n, HMC_LOGIT_MAX_N);
+  if (k->minv_full || k->p_chol_t || k->kick)
+    return fail(HMC_ENOTSUP, "%s: a full cov_p is not supported for logistic targets (diagonal minv/p_scale only)", what);
+  return HMC_OK;
+}
+
+hmc_target logit_shape(const hmc_logistic* m) { return hmc_target{m->D, HMC_TARGET_DIAG, nullptr, nullptr, 0.0}; }
+
+hmc::LogitArgs logit_args(const hmc_logistic* m, const hmc::RandArgs& a) {
+  hmc::LogitArgs x{};
+  x.a = a;
+  x.nrows = m->n;
+  x.ldx = m->ldx;
+  x.X = m->X;
+  x.y = m->y;
+  x.pprec = m->prior_prec;
+  return x;
+}
+
+// Row-wise entries: the rows take the chains' place in the 16-column tiles.
+hmc::LogitArgs logit_row_args(const hmc_logistic* m, const hmc_kinetic* k, int64_t n) {
+  hmc::RandArgs a{};
+  a.n = n;
+  a.D = m->D;
+  a.dt = k->dt;
+  a.h = k->dt * 0.5;
+  a.minv = k->minv;
+  a.dtv = k->dt_vec;
+  return logit_args(m, a);
+}
+
+}  // namespace
+
+hmc_status hmc_logit_chain_init(const hmc_logistic* m, const hmc_kinetic* k, const hmc_schedule* s,
+                                const hmc_replay* r, const double* q_start, hmc_state* st, void* stream) {
+  if (hmc_status e = check_logistic(m, k, "hmc_logit_chain_init")) return e;
+  const hmc_target t = logit_shape(m);
+  if (hmc_status e = check_schedule(&t, k, s, false)) return e;
+  if (!st) return fail(HMC_EINVAL, "null state");
+  if (s->n_chains == 0) return HMC_OK;   // empty batch: zero-size buffers may be NULL
+  if (!st->q || !st->E_prev || !q_start) return fail(HMC_EINVAL, "null state/q_start");
+  const bool replay = s->rng_mode == HMC_RNG_REPLAY;
+  if (replay && (!r || !r->p0)) return fail(HMC_EINVAL, "replay mode needs p0");
+  const hmc::Layout lay{0, 0, 0, (m->D + 1) / 2};
+  hmc::RandArgs a = rand_args(&t, k, s, replay ? r : nullptr, st, lay);
+  a.qstart = q_start;
+  return hip_status(hmc::launch_logit_init(logit_args(m, a), replay, (hipStream_t)stream), "hmc_logit_chain_init");
+}
+
+hmc_status hmc_logit_random_iters(const hmc_logistic* m, const hmc_kinetic* k, const hmc_schedule* s,
+                                  const hmc_replay* r, hmc_state* st, void* stream) {
+  if (hmc_status e = check_logistic(m, k, "hmc_logit_random_iters")) return e;
+  const hmc_target t = logit_shape(m);
+  if (hmc_status e = check_schedule(&t, k, s, true)) return e;
+  if (!st) return fail(HMC_EINVAL, "null state");
+  if (hmc_status e = check_window(&t, s, st)) return e;
+  if (s->iter_begin < 1 || s->iter_end < s->iter_begin || s->iter_end > s->n_iter + 1)
+    return fail(HMC_EINVAL, "iteration range must satisfy 1 <= begin <= end <= Niter+1");
+  if (s->n_chains == 0) return HMC_OK;   // empty batch: zero-size buffers may be NULL
+  if (!st->q || !st->E_prev) return fail(HMC_EINVAL, "null state");
+  const bool replay = s->rng_mode == HMC_RNG_REPLAY;
+  if (replay && (!r || !r->p || !r->L || !r->lnu)) return fail(HMC_EINVAL, "replay mode needs p, L, lnu");
+  if (s->iter_end == s->iter_begin) return HMC_OK;
+  if (st->n_save > 0 && st->traj_q && st->traj_stride < s->L_high)
+    return fail(HMC_EINVAL, "traj_stride must be >= L_high");
+  const hmc::Layout lay{0, 0, 0, (m->D + 1) / 2};
+  const hmc::RandArgs a = rand_args(&t, k, s, replay ? r : nullptr, st, lay);
+  return hip_status(hmc::launch_logit_iters(logit_args(m, a), replay, (hipStream_t)stream), "hmc_logit_random_iters");
+}
+
+hmc_status hmc_logit_leapfrog(const hmc_logistic* m, const hmc_kinetic* k, int64_t n, const double* p, const double* q,
+                              double* p_out, double* q_out, void* stream) {
+  if (hmc_status e = check_logistic(m, k, "hmc_logit_leapfrog")) return e;
+  if (n < 0) return fail(HMC_EINVAL, "bad arguments");
+  if (n > 0 && (!p || !q || !p_out || !q_out)) return fail(HMC_EINVAL, "null row pointers");
+  if (p_out == p || q_out == q || p_out == q || q_out == p) return fail(HMC_EINVAL, "outputs alias inputs");
+  if (!std::isfinite(k->dt) && !k->dt_vec) return fail(HMC_EINVAL, "dt must be set (samplers.py:332)");
+  hmc::LogitArgs x = logit_row_args(m, k, n);
+  x.row_p = p;
+  x.row_q = q;
+  x.row_po = p_out;
+  x.row_qo = q_out;
+  return hip_status(hmc::launch_logit_rows(x, true, (hipStream_t)stream), "hmc_logit_leapfrog");
+}
+
+hmc_status hmc_logit_energy(const hmc_logistic* m, const hmc_kinetic* k, int64_t n, const double* q, const double* p,
+                            double* E_out, void* stream) {
+  if (hmc_status e = check_logistic(m, k, "hmc_logit_energy")) return e;
+  if (n < 0) return fail(HMC_EINVAL, "bad arguments");
+  if (n > 0 && (!p || !q || !E_out)) return fail(HMC_EINVAL, "null row pointers");
+  hmc::LogitArgs x = logit_row_args(m, k, n);
+  x.row_p = p;
+  x.row_q = q;
+  x.row_E = E_out;
+  return hip_status(hmc::launch_logit_rows(x, false, (hipStream_t)stream), "hmc_logit_energy");
 }
 
 hmc_status hmc_rng_normals(uint64_t seed, int64_t chain0, int64_t n, int32_t iteration, int32_t npairs, double* out,

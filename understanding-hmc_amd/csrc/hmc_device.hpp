@@ -139,6 +139,26 @@ __device__ __forceinline__ double fast_log(double x) {
   return __builtin_fma(dk, 6.93147180369123816490e-01, -((hfsq - inner) - f));
 }
 
+// exp(x), ~1 ulp, for any x (fdlibm e_exp.c: x = k ln2 + r, |r| <= ln2/2, exp(r) from the
+// rational form of its Remez polynomial; 2^k by v_ldexp_f64, which also rounds into the
+// subnormals).  NaN propagates; x below log(min subnormal) gives 0.  (hmc_mix.hip, hmc_logit.hip)
+__device__ __forceinline__ double fast_exp(double x) {
+  x = x < -746.0 ? -746.0 : x;
+  x = x > 710.0 ? 710.0 : x;
+  const double kf = __builtin_rint(x * 1.44269504088896338700e+00);
+  const double hi = __builtin_fma(-kf, 6.93147180369123816490e-01, x);   // exact: ln2_hi has 21 low zero bits
+  const double lo = kf * 1.90821492927058770002e-10;
+  const double r = hi - lo;
+  const double t = r * r;
+  double pc = fmac_k(t, 4.13813679705723846039e-08, -1.65339022054652515390e-06);   // P5, P4
+  pc = fmac_k(t, pc, 6.61375632143793436117e-05);                                     // P3
+  pc = fmac_k(t, pc, -2.77777777770155933842e-03);                                    // P2
+  pc = fmac_k(t, pc, 1.66666666666666019037e-01);                                     // P1
+  const double c = __builtin_fma(-t, pc, r);
+  const double y = 1.0 - ((lo - (r * c) * rcp_nr(2.0 - c)) - hi);
+  return __builtin_ldexp(y, (int)kf);
+}
+
 // sqrt(x) for x >= 0: v_rsq_f64 seed + one Goldschmidt/Newton refinement.
 __device__ __forceinline__ double fast_sqrt(double x) {
   const double y = __builtin_amdgcn_rsq(x);

@@ -23,7 +23,7 @@
 // with the gradient at q_new reused as the next step's q_old gradient.  E = V(q) + sum p_d minv_d p_d / 2;
 // accept iff (dE < 0) || (log u < -dE): a NaN or infinite energy rejects.
 //
-// One arithmetic for both fp_mode values: exp and log are ~1 ulp fdlibm-style fp64 (fast_exp below,
+// One arithmetic for both fp_mode values: exp and log are ~1 ulp fdlibm-style fp64 (fast_exp and
 // fast_log of hmc_device.hpp), which cannot be bit-identical to NumPy's, so there is no EXACT
 // instance.  Built with -ffp-contract=off; the FMAs are explicit.
 #include "hmc_device.hpp"
@@ -34,26 +34,6 @@ namespace hmc {
 namespace {
 
 constexpr int kMixK = HMC_MIX_MAX_COMPONENTS;
-
-// exp(x), ~1 ulp, for any x (fdlibm e_exp.c: x = k ln2 + r, |r| <= ln2/2, exp(r) from the
-// rational form of its Remez polynomial; 2^k by v_ldexp_f64, which also rounds into the
-// subnormals).  NaN propagates; x below log(min subnormal) gives 0.
-__device__ __forceinline__ double fast_exp(double x) {
-  x = x < -746.0 ? -746.0 : x;
-  x = x > 710.0 ? 710.0 : x;
-  const double kf = __builtin_rint(x * 1.44269504088896338700e+00);
-  const double hi = __builtin_fma(-kf, 6.93147180369123816490e-01, x);   // exact: ln2_hi has 21 low zero bits
-  const double lo = kf * 1.90821492927058770002e-10;
-  const double r = hi - lo;
-  const double t = r * r;
-  double pc = fmac_k(t, 4.13813679705723846039e-08, -1.65339022054652515390e-06);   // P5, P4
-  pc = fmac_k(t, pc, 6.61375632143793436117e-05);                                     // P3
-  pc = fmac_k(t, pc, -2.77777777770155933842e-03);                                    // P2
-  pc = fmac_k(t, pc, 1.66666666666666019037e-01);                                     // P1
-  const double c = __builtin_fma(-t, pc, r);
-  const double y = 1.0 - ((lo - (r * c) * rcp_nr(2.0 - c)) - hi);
-  return __builtin_ldexp(y, (int)kf);
-}
 
 struct Lane {
   int lane, g, s, base;

@@ -18,6 +18,7 @@ HMC_MODE_EXACT, HMC_MODE_FAST = 0, 1
 NCOUNTERS = 9
 COUNTER_SLOTS = 4096   # include/hmc.h HMC_COUNTER_SLOTS: counters buffer is [slots][NCOUNTERS]
 MIX_MAX_COMPONENTS, MIX_MAX_D = 8, 512   # include/hmc.h HMC_MIX_MAX_COMPONENTS, HMC_MIX_MAX_D
+LOGIT_MAX_D, LOGIT_MAX_N = 128, 1 << 20   # include/hmc.h HMC_LOGIT_MAX_D, HMC_LOGIT_MAX_N
 
 c_dp = ctypes.c_void_p  # device pointers are passed as integers (torch data_ptr())
 
@@ -56,6 +57,12 @@ class Mixture(ctypes.Structure):
     """hmc_mixture: K Gaussians with diagonal covariances (device pointers)."""
     _fields_ = [("D", ctypes.c_int32), ("K", ctypes.c_int32), ("logw", c_dp), ("mu", c_dp), ("prec", c_dp),
                 ("logdet_const", c_dp)]
+
+
+class Logistic(ctypes.Structure):
+    """hmc_logistic: design matrix, labels and prior precisions (device pointers)."""
+    _fields_ = [("D", ctypes.c_int32), ("n", ctypes.c_int32), ("ldx", ctypes.c_int64), ("X", c_dp), ("y", c_dp),
+                ("prior_prec", c_dp)]
 
 
 # Exported symbols (tests check every one of these is present; keep in sync with include/hmc.h)
@@ -104,6 +111,16 @@ SYMBOLS = {
                                         c_dp, c_dp, c_dp]),
     "hmc_mix_energy": (ctypes.c_int, [ctypes.POINTER(Mixture), ctypes.POINTER(Kinetic), ctypes.c_int64, c_dp, c_dp,
                                       c_dp, c_dp]),
+    "hmc_logit_chain_init": (ctypes.c_int, [ctypes.POINTER(Logistic), ctypes.POINTER(Kinetic),
+                                            ctypes.POINTER(Schedule), ctypes.POINTER(Replay), c_dp,
+                                            ctypes.POINTER(State), c_dp]),
+    "hmc_logit_random_iters": (ctypes.c_int, [ctypes.POINTER(Logistic), ctypes.POINTER(Kinetic),
+                                              ctypes.POINTER(Schedule), ctypes.POINTER(Replay),
+                                              ctypes.POINTER(State), c_dp]),
+    "hmc_logit_leapfrog": (ctypes.c_int, [ctypes.POINTER(Logistic), ctypes.POINTER(Kinetic), ctypes.c_int64, c_dp,
+                                          c_dp, c_dp, c_dp, c_dp]),
+    "hmc_logit_energy": (ctypes.c_int, [ctypes.POINTER(Logistic), ctypes.POINTER(Kinetic), ctypes.c_int64, c_dp, c_dp,
+                                        c_dp, c_dp]),
     "hmc_rng_normals": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                        ctypes.c_int32, c_dp, c_dp]),
     "hmc_philox": (ctypes.c_int, [ctypes.c_uint32] * 6 + [ctypes.c_int64, c_dp, c_dp]),

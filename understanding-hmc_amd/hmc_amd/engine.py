@@ -316,11 +316,15 @@ class RandomEngine:
         return self.counters.cpu().numpy().astype(np.int64).sum(axis=0)
 
 
-class MixtureEngine(RandomEngine):
-    """Chain batch of the Random-trajectory sampler on a MixtureTarget (hmc_mix_chain_init /
-    hmc_mix_random_iters, csrc/hmc_mix.hip): RandomEngine's surface, state and outputs, with the
-    mixture descriptor in place of the MVN one.  Diagonal cov_p only, D <= 512, K <= 8; `fp_mode`
-    is accepted and changes nothing (one arithmetic: exp / log cannot be bit-identical to NumPy's)."""
+class _KernelTargetEngine(RandomEngine):
+    """What the engines of the targets with kernels of their own share (MixtureEngine,
+    LogisticEngine): RandomEngine's surface, state and outputs, a target descriptor of their own in
+    place of the MVN one, a diagonal cov_p only, no workspace, and a pair of C entries that take that
+    descriptor.  `fp_mode` is accepted and changes nothing (one arithmetic: exp / log cannot be
+    bit-identical to NumPy's)."""
+
+    _init_entry = _run_entry = None      # names of the hmc_*_chain_init / hmc_*_random_iters entries
+    _what = "these"
 
     def __init__(self, target, n_chains, n_iter, warm_up, thin, L_low, L_high, dt, cov_p=None, rng="philox",
                  seed=0, fp_mode="fast", chain_offset=0, store_chain=True, store_energy=True, n_save=0,
@@ -329,23 +333,18 @@ class MixtureEngine(RandomEngine):
                          fp_mode=fp_mode, chain_offset=chain_offset, store_chain=store_chain,
                          store_energy=store_energy, n_save=n_save, device=device)
 
-    @staticmethod
-    def check_supported(target, cov_p):
-        """NotImplementedError, before anything touches the device, for what the kernels do not take."""
-        if target.D > H.MIX_MAX_D or target.K > H.MIX_MAX_COMPONENTS:
-            raise NotImplementedError("mixture kernels: D=%d, K=%d (D <= %d, K <= %d)"
-                                      % (target.D, target.K, H.MIX_MAX_D, H.MIX_MAX_COMPONENTS))
+    @classmethod
+    def _check_diag_mass(cls, cov_p):
         if cov_p is not None:
             cov_p = np.asarray(cov_p, dtype=np.float64)
             if np.any(cov_p - np.diag(np.diag(cov_p))):
-                raise NotImplementedError("mixture kernels: a full cov_p is not supported (diagonal only)")
+                raise NotImplementedError("%s kernels: a full cov_p is not supported (diagonal only)" % cls._what)
 
-    def _descriptors(self, target, cov_p, dt, dense):
-        self.check_supported(target, cov_p)
+    def _kinetic(self, cov_p, dt):
+        """self.K for a diagonal cov_p (its device arrays kept alive on the object)."""
         D, dev = self.D, self.device
         cov_p = np.diag(np.ones(D)) if cov_p is None else np.asarray(cov_p, dtype=np.float64)
         self.cov_p = cov_p
-        self._mix = [_dev(a, dev) for a in (target.logw, target.mu, target.prec, target.logdet_const)]
         minv = np.diag(np.linalg.inv(cov_p)).astype(np.float64)          # samplers.py:356
         ident_mass = bool(np.all(np.diag(cov_p) == 1.0) and np.all(minv == 1.0))
         self._minv = None if ident_mass else _dev(minv, dev)
@@ -358,28 +357,79 @@ class MixtureEngine(RandomEngine):
         else:
             assert dt.size == D
             self._dtv, dts = _dev(dt.reshape(-1), dev), 0.0
-        self.T = H.Mixture(D, target.K, *[H.ptr(x) for x in self._mix])
         self.K = H.Kinetic(H.ptr(self._minv), H.ptr(self._pscale), H.ptr(self._dtv), dts, None, None, None)
-        return None
 
     def _alloc_workspace(self, kind, order_tiles, random_ws):
-        self._order, self._order_bytes = None, 0        # hmc_state.order is ignored by the mixture calls
-
-    def _target_arrays(self):
-        t = self.t
-        return (t.logw, t.mu, t.prec, t.logdet_const)
+        self._order, self._order_bytes = None, 0        # hmc_state.order is ignored by these calls
 
     def init(self, q_start):
         qs = q_start if isinstance(q_start, torch.Tensor) else _dev(np.asarray(q_start).reshape(self.N, self.D),
                                                                     self.device)
         self._qs = qs.to(self.device, torch.float64).contiguous()
-        H.check(H.lib().hmc_mix_chain_init(self.T, self.K, self.schedule(1, 1), self._replay, H.ptr(self._qs), self.S,
-                                           self.stream()), "hmc_mix_chain_init")
+        H.check(getattr(H.lib(), self._init_entry)(self.T, self.K, self.schedule(1, 1), self._replay, H.ptr(self._qs),
+                                                   self.S, self.stream()), self._init_entry)
 
     def run(self, it0, it1):
         """Iterations [it0, it1) of every chain in ONE fused kernel launch."""
-        H.check(H.lib().hmc_mix_random_iters(self.T, self.K, self.schedule(it0, it1), self._replay, self.S,
-                                             self.stream()), "hmc_mix_random_iters")
+        H.check(getattr(H.lib(), self._run_entry)(self.T, self.K, self.schedule(it0, it1), self._replay, self.S,
+                                                  self.stream()), self._run_entry)
+
+
+class MixtureEngine(_KernelTargetEngine):
+    """Chain batch of the Random-trajectory sampler on a MixtureTarget (hmc_mix_chain_init /
+    hmc_mix_random_iters, csrc/hmc_mix.hip): RandomEngine's surface, state and outputs, with the
+    mixture descriptor in place of the MVN one.  Diagonal cov_p only, D <= 512, K <= 8; `fp_mode`
+    is accepted and changes nothing (one arithmetic: exp / log cannot be bit-identical to NumPy's)."""
+
+    _init_entry, _run_entry, _what = "hmc_mix_chain_init", "hmc_mix_random_iters", "mixture"
+
+    @classmethod
+    def check_supported(cls, target, cov_p):
+        """NotImplementedError, before anything touches the device, for what the kernels do not take."""
+        if target.D > H.MIX_MAX_D or target.K > H.MIX_MAX_COMPONENTS:
+            raise NotImplementedError("mixture kernels: D=%d, K=%d (D <= %d, K <= %d)"
+                                      % (target.D, target.K, H.MIX_MAX_D, H.MIX_MAX_COMPONENTS))
+        cls._check_diag_mass(cov_p)
+
+    def _descriptors(self, target, cov_p, dt, dense):
+        self.check_supported(target, cov_p)
+        self._mix = [_dev(a, self.device) for a in (target.logw, target.mu, target.prec, target.logdet_const)]
+        self._kinetic(cov_p, dt)
+        self.T = H.Mixture(self.D, target.K, *[H.ptr(x) for x in self._mix])
+        return None
+
+    def _target_arrays(self):
+        t = self.t
+        return (t.logw, t.mu, t.prec, t.logdet_const)
+
+
+class LogisticEngine(_KernelTargetEngine):
+    """Chain batch of the Random-trajectory sampler on a LogisticTarget (hmc_logit_chain_init /
+    hmc_logit_random_iters, csrc/hmc_logit.hip: 16 chains per wave, both products of the gradient
+    on the f64 matrix cores).  Diagonal cov_p only, D <= 128, n <= 2^20; `fp_mode` is accepted and
+    changes nothing.  A checkpoint fingerprints the data (X, y, 1 / prior_var)."""
+
+    _init_entry, _run_entry, _what = "hmc_logit_chain_init", "hmc_logit_random_iters", "logistic"
+
+    @classmethod
+    def check_supported(cls, target, cov_p):
+        """NotImplementedError, before anything touches the device, for what the kernels do not take."""
+        if target.D > H.LOGIT_MAX_D or target.n > H.LOGIT_MAX_N:
+            raise NotImplementedError("logistic kernels: D=%d, n=%d (D <= %d, n <= %d)"
+                                      % (target.D, target.n, H.LOGIT_MAX_D, H.LOGIT_MAX_N))
+        cls._check_diag_mass(cov_p)
+
+    def _descriptors(self, target, cov_p, dt, dense):
+        self.check_supported(target, cov_p)
+        # X as it is, row-major with ldx = D: the kernel clamps its reads to [n][D]
+        self._data = [_dev(a, self.device) for a in (target.X, target.y, target.prior_prec)]
+        self._kinetic(cov_p, dt)
+        self.T = H.Logistic(self.D, target.n, self.D, *[H.ptr(x) for x in self._data])
+        return None
+
+    def _target_arrays(self):
+        t = self.t
+        return (t.X, t.y, t.prior_prec)
 
 
 class NutsEngine(RandomEngine):

@@ -25,13 +25,31 @@ import torch
 
 from . import _lib as H
 from .diagnostics import StreamingDiagnostics
-from .engine import MixtureEngine, NutsEngine, RandomEngine
-from .target import MixtureTarget, MVNTarget, probe_closures  # noqa: F401
+from .engine import LogisticEngine, MixtureEngine, NutsEngine, RandomEngine
+from .target import LogisticTarget, MixtureTarget, MVNTarget, probe_closures  # noqa: F401
 from . import utils as U
 
 
 def _dev_tensor(a, device, dtype=torch.float64):
     return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(device)
+
+
+def _mixture_descriptor(t, up):
+    keep = [up(a) for a in (t.logw, t.mu, t.prec, t.logdet_const)]
+    return H.Mixture(t.D, t.K, *[H.ptr(x) for x in keep]), keep
+
+
+def _logistic_descriptor(t, up):
+    keep = [up(a) for a in (t.X, t.y, t.prior_prec)]
+    return H.Logistic(t.D, t.n, t.D, *[H.ptr(x) for x in keep]), keep
+
+
+# Targets that are not MVN and have kernels of their own: (name, engine, device descriptor for the
+# row-wise calls, leapfrog entry, energy entry).  Random sampler and a diagonal cov_p only.
+_KERNEL_TARGETS = {
+    MixtureTarget: ("mixture", MixtureEngine, _mixture_descriptor, "hmc_mix_leapfrog", "hmc_mix_energy"),
+    LogisticTarget: ("logistic", LogisticEngine, _logistic_descriptor, "hmc_logit_leapfrog", "hmc_logit_energy"),
+}
 
 
 class sampler(object):
@@ -76,14 +94,18 @@ class sampler(object):
 
 
 class HMC_sampler(sampler):
-    """HMC sampler for a multivariate-normal (or Gaussian-mixture) target on MI355X (samplers.py:297-924).
+    """HMC sampler for a multivariate-normal (or Gaussian-mixture, or logistic-regression) target on
+    MI355X (samplers.py:297-924).
 
     Extra optional kwargs (all new; defaults keep the reference behaviour):
       target   : MVNTarget; if None, V/dVdq are affine-probed (target.probe_closures).  Or a
                  MixtureTarget (K Gaussians with diagonal covariances; sampler_type="Random", a
                  diagonal cov_p, D <= 512, K <= 8: anything else raises NotImplementedError here,
-                 before any launch; fp_mode changes nothing for it).  With a target, V / dVdq may
-                 be None: they are set to the target's host methods
+                 before any launch; fp_mode changes nothing for it).  Or a LogisticTarget (design
+                 matrix X (n, D), labels y, normal prior; sampler_type="Random", a diagonal cov_p,
+                 D <= 128, n <= 2^20: anything else raises NotImplementedError here; fp_mode changes
+                 nothing for it either).  With a target, V / dVdq may be None: they are set to the
+                 target's host methods
       rng      : "replay" | "philox"
       seed     : Philox key (rng="philox")
       fp_mode  : "exact" (reference rounding, no FMA) | "fast" (FMA-contracted integrator)
@@ -150,12 +172,13 @@ class HMC_sampler(sampler):
                 self.V = target.V
             if self.dVdq is None:
                 self.dVdq = target.dVdq
-        self._mixture = isinstance(target, MixtureTarget)
-        if self._mixture:
+        self._kernel_target = next((v for k, v in _KERNEL_TARGETS.items() if isinstance(target, k)), None)  # None: MVN
+        if self._kernel_target:
+            name, engine = self._kernel_target[:2]
             assert target.D == self.D
             if self.sampler_type == "NUTS":
-                raise NotImplementedError("NUTS on a mixture target is not supported (sampler_type='Random')")
-            MixtureEngine.check_supported(target, self.cov_p)
+                raise NotImplementedError("NUTS on a %s target is not supported (sampler_type='Random')" % name)
+            engine.check_supported(target, self.cov_p)
         self.n_leapfrog = 0
         self.q_chain_device = None
 
@@ -165,12 +188,12 @@ class HMC_sampler(sampler):
             self._target = probe_closures(self.D, self.V, self.dVdq)
         return self._target
 
-    def _mix_descriptors(self):
-        """hmc_mixture + hmc_kinetic of a MixtureTarget (diagonal cov_p) for the row-wise calls."""
+    def _kernel_target_descriptors(self):
+        """The target's own descriptor (hmc_mixture / hmc_logistic) + hmc_kinetic (diagonal cov_p)
+        for the row-wise calls."""
         t, dev = self._target, self.device
         cov_p = np.asarray(self.cov_p, dtype=np.float64)
-        keep = [_dev_tensor(a, dev) for a in (t.logw, t.mu, t.prec, t.logdet_const)]
-        M = H.Mixture(self.D, t.K, *[H.ptr(x) for x in keep])
+        M, keep = self._kernel_target[2](t, lambda a: _dev_tensor(a, dev))
         minv_d = np.diag(self.inv_cov_p).astype(np.float64)
         ident_mass = np.all(np.diag(cov_p) == 1.0) and np.all(minv_d == 1.0)
         minv = None if ident_mass else _dev_tensor(minv_d, dev)
@@ -263,7 +286,8 @@ class HMC_sampler(sampler):
         assert q_start.shape[0] == self.Nchain                                    # :396
         torch.cuda.set_device(self.device)
         n_save = int(N_save_chain0) if N_save_chain0 > 0 else 0
-        engine = MixtureEngine if self._mixture else RandomEngine       # hmc_mix.hip / the MVN kernels
+        # the target's own kernels (hmc_mix.hip, hmc_logit.hip) or the MVN kernels
+        engine = self._kernel_target[1] if self._kernel_target else RandomEngine
         eng = engine(self.target(), self.Nchain, self.Niter, self.warm_up_num, self.thin_rate, self.L_low,
                      self.L_high, self.dt, cov_p=self.cov_p, rng=self.rng, seed=self.seed,
                      fp_mode=self.fp_mode, chain_offset=self.chain_offset, store_chain=self.store_chain,
@@ -430,14 +454,15 @@ class HMC_sampler(sampler):
         """samplers.py:831-839 for one (p, q) row or a batch of rows, on the GPU."""
         p = np.atleast_2d(np.asarray(p_old, dtype=np.float64))
         q = np.atleast_2d(np.asarray(q_old, dtype=np.float64))
-        T, K, keep = self._mix_descriptors() if self._mixture else self._descriptors()
+        T, K, keep = self._kernel_target_descriptors() if self._kernel_target else self._descriptors()
         dev = self.device
         pt, qt = _dev_tensor(p, dev), _dev_tensor(q, dev)
         po, qo = torch.empty_like(pt), torch.empty_like(qt)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        if self._mixture:
-            H.check(H.lib().hmc_mix_leapfrog(T, K, p.shape[0], H.ptr(pt), H.ptr(qt), H.ptr(po), H.ptr(qo), stream),
-                    "hmc_mix_leapfrog")
+        if self._kernel_target:
+            entry = self._kernel_target[3]
+            H.check(getattr(H.lib(), entry)(T, K, p.shape[0], H.ptr(pt), H.ptr(qt), H.ptr(po), H.ptr(qo), stream),
+                    entry)
         else:
             H.check(H.lib().hmc_leapfrog(T, K, p.shape[0], H.ptr(pt), H.ptr(qt), H.ptr(po), H.ptr(qo),
                                          H.HMC_MODE_EXACT if self.fp_mode == "exact" else H.HMC_MODE_FAST,
@@ -451,12 +476,12 @@ class HMC_sampler(sampler):
         """samplers.py:819-823 (V of utils.py:218 + K of :817) for one row or a batch."""
         qq = np.atleast_2d(np.asarray(q, dtype=np.float64))
         pp = np.atleast_2d(np.asarray(p, dtype=np.float64))
-        T, K, keep = self._mix_descriptors() if self._mixture else self._descriptors()
+        T, K, keep = self._kernel_target_descriptors() if self._kernel_target else self._descriptors()
         dev = self.device
         qt, pt = _dev_tensor(qq, dev), _dev_tensor(pp, dev)
         Et = torch.empty(qq.shape[0], dtype=torch.float64, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        energy = H.lib().hmc_mix_energy if self._mixture else H.lib().hmc_energy
+        energy = getattr(H.lib(), self._kernel_target[4]) if self._kernel_target else H.lib().hmc_energy
         H.check(energy(T, K, qq.shape[0], H.ptr(qt), H.ptr(pt), H.ptr(Et), stream), "hmc_energy")
         E = Et.cpu().numpy()
         return E[0] if np.ndim(q) == 1 else E

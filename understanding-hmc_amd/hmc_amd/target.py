@@ -16,6 +16,8 @@ Closures that are not MVN are rejected (no CPU fallback exists in the product).
 One target that is not MVN has kernels of its own: `MixtureTarget(weights, mus, variances)`,
 a mixture of K Gaussians with diagonal covariances (csrc/hmc_mix.hip), passed as
 HMC_sampler(D, None, None, ..., target=MixtureTarget(...), sampler_type="Random").
+One target is defined by data: `LogisticTarget(X, y, prior_var)`, the posterior of logistic-regression
+coefficients under a normal prior (csrc/hmc_logit.hip), passed the same way.
 """
 import numpy as np
 
@@ -118,6 +120,63 @@ class MixtureTarget:
         """n exact draws from a np.random.RandomState (start points, tests)."""
         k = rng.choice(self.K, size=n, p=self.w)
         return self.mu[k] + np.sqrt(self.variances[k]) * rng.standard_normal((n, self.D))
+
+
+class LogisticTarget:
+    """Bayesian logistic regression: design matrix X (n, D), labels y (n,) in {0, 1}, independent
+    zero-mean normal prior of variance prior_var (a scalar or (D,)).
+
+    With z = X q and no normalising constants
+        V(q)    = sum_j [softplus(z_j) - y_j z_j] + 0.5 sum_d q_d^2 / prior_var_d
+        dV/dq   = X^T (sigma(z) - y) + q / prior_var
+        softplus(z) = max(z, 0) + log1p(exp(-|z|)),  sigma(z) = 1/(1+e^-z) (z >= 0), e^z/(1+e^z) (z < 0):
+    forms that never overflow.  The host V / dVdq below serve HMC_sampler.V / .dVdq and the plots,
+    for one row or for batched (..., D) rows; the chains run in csrc/hmc_logit.hip from the device
+    descriptor's arrays X, y and prior_prec = 1 / prior_var.  `q0` is the prior mean, zeros(D)
+    (what the MVN targets call q0: where start points and plots centre)."""
+
+    diagonal = True
+
+    def __init__(self, X, y, prior_var=1.0):
+        self.X = np.ascontiguousarray(X, dtype=np.float64)
+        self.y = np.ascontiguousarray(y, dtype=np.float64)
+        if self.X.ndim != 2 or self.X.shape[0] < 1 or self.X.shape[1] < 1:
+            raise AssertionError("LogisticTarget takes X (n, D) with n >= 1 and D >= 1")
+        if self.y.shape != (self.X.shape[0],):
+            raise AssertionError("LogisticTarget takes y (n,) with one label per row of X")
+        if not np.all((self.y == 0.0) | (self.y == 1.0)):
+            raise AssertionError("logistic labels must be 0 or 1")
+        pv = np.asarray(prior_var, dtype=np.float64)
+        if pv.ndim == 0:
+            pv = np.full(self.D, float(pv))
+        self.prior_var = np.ascontiguousarray(pv)
+        if self.prior_var.shape != (self.D,):
+            raise AssertionError("prior_var must be a scalar or (D,)")
+        if not np.all(self.prior_var > 0):
+            raise AssertionError("prior_var must be positive")
+        self.prior_prec = 1.0 / self.prior_var
+        self.q0 = np.zeros(self.D)
+
+    @property
+    def D(self):
+        return self.X.shape[1]
+
+    @property
+    def n(self):
+        return self.X.shape[0]
+
+    def V(self, q):
+        q = np.asarray(q, dtype=np.float64)
+        z = q @ self.X.T                                            # (..., n)
+        softplus = np.maximum(z, 0.0) + np.log1p(np.exp(-np.abs(z)))
+        return np.sum(softplus - self.y * z, axis=-1) + 0.5 * np.sum(q * q * self.prior_prec, axis=-1)
+
+    def dVdq(self, q):
+        q = np.asarray(q, dtype=np.float64)
+        z = q @ self.X.T
+        t = np.exp(-np.abs(z))
+        sigma = np.where(z >= 0, 1.0, t) / (1.0 + t)
+        return (sigma - self.y) @ self.X + q * self.prior_prec
 
 
 def probe_closures(D, V, dVdq, n_check=4, rtol=1e-9, seed=12345):
