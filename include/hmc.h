@@ -370,6 +370,71 @@ hmc_status hmc_logit_leapfrog(const hmc_logistic* m, const hmc_kinetic* k, int64
 hmc_status hmc_logit_energy(const hmc_logistic* m, const hmc_kinetic* k, int64_t n, const double* q,
                             const double* p, double* E_out, void* stream);
 
+/* ---------------------------------------------------------------- generalized linear models
+ * The logistic target above is one family of a generalized linear model: data (X, y), a linear
+ * predictor z = X q, a per-row negative log-likelihood and the same normal prior.  hmc_glm names
+ * the family; the kernels are the logistic ones with the family as a template parameter
+ * (hmc_logit.hip), plus a No-U-Turn kernel (hmc_glm_nuts.hip).  No normalising constants:
+ *   HMC_GLM_BERNOULLI  exactly the logistic target: V, dV/dq as above, y in {0, 1}
+ *   HMC_GLM_POISSON    log link, y = 0, 1, 2, ...:
+ *                      V(q)  = sum_j [ exp(z_j) - y_j z_j ] + 0.5 sum_d prior_prec_d q_d^2
+ *                      dV/dq = X^T (exp(z) - y) + prior_prec q
+ *                      exp(z) is +inf from z ~ 709.78 on: that chain's V is +inf.  The Random sampler
+ *                      rejects such a proposal ((dE < 0) || (log u < -dE) is false, also for NaN),
+ *                      NUTS counts +inf as unstable (|E - E_init| > 1000); NaN compares false in both,
+ *                      as in NumPy.  A non-finite chain changes nothing in its tile's other chains. */
+enum { HMC_GLM_BERNOULLI = 0, HMC_GLM_POISSON = 1 };
+typedef struct hmc_glm {
+  int32_t D, n;               /* 1 <= D <= HMC_LOGIT_MAX_D, 1 <= n <= HMC_LOGIT_MAX_N        */
+  int64_t ldx;                /* row stride of X in doubles, >= D                            */
+  const double* X;            /* [n][ldx] design matrix, row-major                           */
+  const double* y;            /* [n] responses                                               */
+  const double* prior_prec;   /* [D] 1 / prior_var                                           */
+  int32_t family;             /* HMC_GLM_BERNOULLI or HMC_GLM_POISSON                        */
+} hmc_glm;                    /* device pointers; 48 bytes: offsets 0, 4, 8, 16, 24, 32, 40  */
+
+/* The four hmc_logit_* entries with hmc_glm in place of hmc_logistic, argument for argument: the
+ * same limits, status codes, draws, counters and invariances; an unknown family is HMC_EINVAL.
+ * With family = HMC_GLM_BERNOULLI they launch the very kernels hmc_logit_* launches (bit-identical
+ * results).  hmc_glm_chain_init serves both samplers. */
+hmc_status hmc_glm_chain_init(const hmc_glm* m, const hmc_kinetic* k, const hmc_schedule* s,
+                              const hmc_replay* r /* NULL for Philox */, const double* q_start, hmc_state* st,
+                              void* stream);
+hmc_status hmc_glm_random_iters(const hmc_glm* m, const hmc_kinetic* k, const hmc_schedule* s,
+                                const hmc_replay* r /* NULL for Philox */, hmc_state* st, void* stream);
+hmc_status hmc_glm_leapfrog(const hmc_glm* m, const hmc_kinetic* k, int64_t n, const double* p,
+                            const double* q, double* p_out, double* q_out, void* stream);
+hmc_status hmc_glm_energy(const hmc_glm* m, const hmc_kinetic* k, int64_t n, const double* q,
+                          const double* p, double* E_out, void* stream);
+
+/* NUTS (samplers.py:495-808, the semantics of hmc_nuts_iters: quirks Q10-Q12, the |E - E_init| >
+ * 1000 guard, d_max and on_dmax) on a GLM target, iterations [iter_begin, iter_end).  One wave owns
+ * a tile of 16 chains for the whole launch and steps it: every chain inside a sub-tree takes one
+ * leapfrog per step through one shared gradient pass; there is no work queue, and the chains of a
+ * tile run through the launch's iterations independently.  State carried between launches: q,
+ * E_prev and, in replay mode, the tape cursors in the workspace tail.
+ * workspace: hmc_glm_nuts_workspace_size(D, n_chains, d_max) bytes (0: D or d_max unsupported),
+ *   caller-owned, zeroed before a run's first call: per 16-chain tile nvec = 8 + 2 (d_max + 1)
+ *   vectors of 16 MT dims (MT = 1, 2, 4 or 8 tiles of 16 dims covering D), element (tile, vec, m,
+ *   lane) at double ((tile nvec + vec) 4 MT + m) 64 + lane, then one int64 tape cursor per chain
+ *   slot (16 per tile).
+ * Draws: the momentum of (chain, it) is the Random entries' (above); the tree's draws come from
+ *   replay->tape (directions and uniforms in the order the reference consumes them) or from Philox
+ *   block (0x80000000 + j, it, global chain) for the j-th draw of an iteration: direction = bit 0
+ *   of word 0, uniform = the 53 bits of words 2, 3.  Results do not depend on the tile column, the
+ *   launch split or chain_offset.
+ * Counters: LEAPFROG = ENERGY_EVALS, UNSTABLE, DMAX, OOB_REJECT (draws past the tape), and
+ *   LEAPFROG_SQ = wave steps: LEAPFROG / (16 LEAPFROG_SQ) is the lane utilisation.
+ *   HANDOFF_GIVEUP is never written.  At d_max the kernel counts and keeps the current sample.
+ * q_chain may be NULL; the circular window qc_rows / qc_row0 is honoured; the chain-0 capture is
+ *   ignored (the reference never fills it for NUTS).
+ * HMC_EINVAL / HMC_ENOTSUP as the entries above, and: HMC_EINVAL for a NULL workspace or
+ *   workspace_bytes below the size query, HMC_ENOTSUP for d_max outside 1 .. 30.  All checks run on
+ *   the host before any launch; an empty batch returns HMC_OK. */
+int64_t hmc_glm_nuts_workspace_size(int32_t D, int64_t n_chains, int32_t d_max);
+hmc_status hmc_glm_nuts_iters(const hmc_glm* m, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
+                              hmc_state* st, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* The standard normals the Philox mode draws for (chain, iteration): out[n][2*npairs].
  * Debug/verification entry (statistical tests of the in-kernel generator). */
 hmc_status hmc_rng_normals(uint64_t seed, int64_t chain0, int64_t n, int32_t iteration,

@@ -707,9 +707,12 @@ hmc::LogitArgs logit_row_args(const hmc_logistic* m, const hmc_kinetic* k, int64
 
 }  // namespace
 
-hmc_status hmc_logit_chain_init(const hmc_logistic* m, const hmc_kinetic* k, const hmc_schedule* s,
-                                const hmc_replay* r, const double* q_start, hmc_state* st, void* stream) {
-  if (hmc_status e = check_logistic(m, k, "hmc_logit_chain_init")) return e;
+// The four entries for either family: hmc_logit_* pass HMC_GLM_BERNOULLI, hmc_glm_* their own.
+namespace {
+
+hmc_status glm_chain_init(const hmc_logistic* m, int family, const hmc_kinetic* k, const hmc_schedule* s,
+                          const hmc_replay* r, const double* q_start, hmc_state* st, void* stream, const char* what) {
+  if (hmc_status e = check_logistic(m, k, what)) return e;
   const hmc_target t = logit_shape(m);
   if (hmc_status e = check_schedule(&t, k, s, false)) return e;
   if (!st) return fail(HMC_EINVAL, "null state");
@@ -720,12 +723,12 @@ hmc_status hmc_logit_chain_init(const hmc_logistic* m, const hmc_kinetic* k, con
   const hmc::Layout lay{0, 0, 0, (m->D + 1) / 2};
   hmc::RandArgs a = rand_args(&t, k, s, replay ? r : nullptr, st, lay);
   a.qstart = q_start;
-  return hip_status(hmc::launch_logit_init(logit_args(m, a), replay, (hipStream_t)stream), "hmc_logit_chain_init");
+  return hip_status(hmc::launch_logit_init(logit_args(m, a), family, replay, (hipStream_t)stream), what);
 }
 
-hmc_status hmc_logit_random_iters(const hmc_logistic* m, const hmc_kinetic* k, const hmc_schedule* s,
-                                  const hmc_replay* r, hmc_state* st, void* stream) {
-  if (hmc_status e = check_logistic(m, k, "hmc_logit_random_iters")) return e;
+hmc_status glm_random_iters(const hmc_logistic* m, int family, const hmc_kinetic* k, const hmc_schedule* s,
+                            const hmc_replay* r, hmc_state* st, void* stream, const char* what) {
+  if (hmc_status e = check_logistic(m, k, what)) return e;
   const hmc_target t = logit_shape(m);
   if (hmc_status e = check_schedule(&t, k, s, true)) return e;
   if (!st) return fail(HMC_EINVAL, "null state");
@@ -741,12 +744,12 @@ hmc_status hmc_logit_random_iters(const hmc_logistic* m, const hmc_kinetic* k, c
     return fail(HMC_EINVAL, "traj_stride must be >= L_high");
   const hmc::Layout lay{0, 0, 0, (m->D + 1) / 2};
   const hmc::RandArgs a = rand_args(&t, k, s, replay ? r : nullptr, st, lay);
-  return hip_status(hmc::launch_logit_iters(logit_args(m, a), replay, (hipStream_t)stream), "hmc_logit_random_iters");
+  return hip_status(hmc::launch_logit_iters(logit_args(m, a), family, replay, (hipStream_t)stream), what);
 }
 
-hmc_status hmc_logit_leapfrog(const hmc_logistic* m, const hmc_kinetic* k, int64_t n, const double* p, const double* q,
-                              double* p_out, double* q_out, void* stream) {
-  if (hmc_status e = check_logistic(m, k, "hmc_logit_leapfrog")) return e;
+hmc_status glm_leapfrog(const hmc_logistic* m, int family, const hmc_kinetic* k, int64_t n, const double* p,
+                        const double* q, double* p_out, double* q_out, void* stream, const char* what) {
+  if (hmc_status e = check_logistic(m, k, what)) return e;
   if (n < 0) return fail(HMC_EINVAL, "bad arguments");
   if (n > 0 && (!p || !q || !p_out || !q_out)) return fail(HMC_EINVAL, "null row pointers");
   if (p_out == p || q_out == q || p_out == q || q_out == p) return fail(HMC_EINVAL, "outputs alias inputs");
@@ -756,19 +759,122 @@ hmc_status hmc_logit_leapfrog(const hmc_logistic* m, const hmc_kinetic* k, int64
   x.row_q = q;
   x.row_po = p_out;
   x.row_qo = q_out;
-  return hip_status(hmc::launch_logit_rows(x, true, (hipStream_t)stream), "hmc_logit_leapfrog");
+  return hip_status(hmc::launch_logit_rows(x, family, true, (hipStream_t)stream), what);
+}
+
+hmc_status glm_energy(const hmc_logistic* m, int family, const hmc_kinetic* k, int64_t n, const double* q,
+                      const double* p, double* E_out, void* stream, const char* what) {
+  if (hmc_status e = check_logistic(m, k, what)) return e;
+  if (n < 0) return fail(HMC_EINVAL, "bad arguments");
+  if (n > 0 && (!p || !q || !E_out)) return fail(HMC_EINVAL, "null row pointers");
+  hmc::LogitArgs x = logit_row_args(m, k, n);
+  x.row_q = q;
+  x.row_p = p;
+  x.row_E = E_out;
+  return hip_status(hmc::launch_logit_rows(x, family, false, (hipStream_t)stream), what);
+}
+
+// hmc_glm -> the data descriptor the kernels take; HMC_EINVAL for a null descriptor or an unknown family
+hmc_status glm_data(const hmc_glm* m, const char* what, hmc_logistic* out) {
+  if (!m) return fail(HMC_EINVAL, "%s: null glm target", what);
+  if (m->family != HMC_GLM_BERNOULLI && m->family != HMC_GLM_POISSON)
+    return fail(HMC_EINVAL, "%s: unknown family %d (HMC_GLM_BERNOULLI, HMC_GLM_POISSON)", what, m->family);
+  *out = hmc_logistic{m->D, m->n, m->ldx, m->X, m->y, m->prior_prec};
+  return HMC_OK;
+}
+
+}  // namespace
+
+hmc_status hmc_logit_chain_init(const hmc_logistic* m, const hmc_kinetic* k, const hmc_schedule* s,
+                                const hmc_replay* r, const double* q_start, hmc_state* st, void* stream) {
+  return glm_chain_init(m, HMC_GLM_BERNOULLI, k, s, r, q_start, st, stream, "hmc_logit_chain_init");
+}
+
+hmc_status hmc_logit_random_iters(const hmc_logistic* m, const hmc_kinetic* k, const hmc_schedule* s,
+                                  const hmc_replay* r, hmc_state* st, void* stream) {
+  return glm_random_iters(m, HMC_GLM_BERNOULLI, k, s, r, st, stream, "hmc_logit_random_iters");
+}
+
+hmc_status hmc_logit_leapfrog(const hmc_logistic* m, const hmc_kinetic* k, int64_t n, const double* p, const double* q,
+                              double* p_out, double* q_out, void* stream) {
+  return glm_leapfrog(m, HMC_GLM_BERNOULLI, k, n, p, q, p_out, q_out, stream, "hmc_logit_leapfrog");
 }
 
 hmc_status hmc_logit_energy(const hmc_logistic* m, const hmc_kinetic* k, int64_t n, const double* q, const double* p,
                             double* E_out, void* stream) {
-  if (hmc_status e = check_logistic(m, k, "hmc_logit_energy")) return e;
-  if (n < 0) return fail(HMC_EINVAL, "bad arguments");
-  if (n > 0 && (!p || !q || !E_out)) return fail(HMC_EINVAL, "null row pointers");
-  hmc::LogitArgs x = logit_row_args(m, k, n);
-  x.row_p = p;
-  x.row_q = q;
-  x.row_E = E_out;
-  return hip_status(hmc::launch_logit_rows(x, false, (hipStream_t)stream), "hmc_logit_energy");
+  return glm_energy(m, HMC_GLM_BERNOULLI, k, n, q, p, E_out, stream, "hmc_logit_energy");
+}
+
+// ---------------------------------------------------------------- generalized-linear-model targets
+hmc_status hmc_glm_chain_init(const hmc_glm* m, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
+                              const double* q_start, hmc_state* st, void* stream) {
+  hmc_logistic d;
+  if (hmc_status e = glm_data(m, "hmc_glm_chain_init", &d)) return e;
+  return glm_chain_init(&d, m->family, k, s, r, q_start, st, stream, "hmc_glm_chain_init");
+}
+
+hmc_status hmc_glm_random_iters(const hmc_glm* m, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
+                                hmc_state* st, void* stream) {
+  hmc_logistic d;
+  if (hmc_status e = glm_data(m, "hmc_glm_random_iters", &d)) return e;
+  return glm_random_iters(&d, m->family, k, s, r, st, stream, "hmc_glm_random_iters");
+}
+
+hmc_status hmc_glm_leapfrog(const hmc_glm* m, const hmc_kinetic* k, int64_t n, const double* p, const double* q,
+                            double* p_out, double* q_out, void* stream) {
+  hmc_logistic d;
+  if (hmc_status e = glm_data(m, "hmc_glm_leapfrog", &d)) return e;
+  return glm_leapfrog(&d, m->family, k, n, p, q, p_out, q_out, stream, "hmc_glm_leapfrog");
+}
+
+hmc_status hmc_glm_energy(const hmc_glm* m, const hmc_kinetic* k, int64_t n, const double* q, const double* p,
+                          double* E_out, void* stream) {
+  hmc_logistic d;
+  if (hmc_status e = glm_data(m, "hmc_glm_energy", &d)) return e;
+  return glm_energy(&d, m->family, k, n, q, p, E_out, stream, "hmc_glm_energy");
+}
+
+int64_t hmc_glm_nuts_workspace_size(int32_t D, int64_t n_chains, int32_t d_max) {
+  return hmc::glm_nuts_ws_doubles(n_chains, D, d_max) * (int64_t)sizeof(double);
+}
+
+hmc_status hmc_glm_nuts_iters(const hmc_glm* m, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
+                              hmc_state* st, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* what = "hmc_glm_nuts_iters";
+  hmc_logistic d;
+  if (hmc_status e = glm_data(m, what, &d)) return e;
+  if (hmc_status e = check_logistic(&d, k, what)) return e;
+  const hmc_target t = logit_shape(&d);
+  if (hmc_status e = check_schedule(&t, k, s, false)) return e;
+  if (!st) return fail(HMC_EINVAL, "null state");
+  if (hmc_status e = check_window(&t, s, st)) return e;
+  if (s->iter_begin < 1 || s->iter_end < s->iter_begin || s->iter_end > s->n_iter + 1)
+    return fail(HMC_EINVAL, "iteration range must satisfy 1 <= begin <= end <= Niter+1");
+  if (s->d_max < 1 || s->d_max > hmc::kNutsDmaxMax)
+    return fail(HMC_ENOTSUP, "%s: d_max=%d, the kernel takes 1 .. %d", what, s->d_max, hmc::kNutsDmaxMax);
+  if (s->n_chains == 0) return HMC_OK;   // empty batch: zero-size buffers may be NULL
+  if (!st->q || !st->E_prev) return fail(HMC_EINVAL, "null state");
+  const bool replay = s->rng_mode == HMC_RNG_REPLAY;
+  if (replay && (!r || !r->p || !r->tape || r->tape_stride < 1)) return fail(HMC_EINVAL, "replay mode needs p and tape");
+  if (!workspace) return fail(HMC_EINVAL, "%s: null workspace", what);
+  const int64_t need = hmc_glm_nuts_workspace_size(d.D, s->n_chains, s->d_max);
+  if (workspace_bytes < need)
+    return fail(HMC_EINVAL, "%s: workspace of %lld bytes, D=%d, %lld chains, d_max=%d need %lld "
+                "(hmc_glm_nuts_workspace_size)", what, (long long)workspace_bytes, d.D, (long long)s->n_chains,
+                s->d_max, (long long)need);
+  if (s->iter_end == s->iter_begin) return HMC_OK;
+  const hmc::Layout lay{0, 0, 16, (d.D + 1) / 2};
+  hmc::RandArgs a = rand_args(&t, k, s, replay ? r : nullptr, st, lay);
+  a.d_max = s->d_max;
+  a.on_dmax = s->on_dmax;
+  a.ws = static_cast<double*>(workspace);
+  if (replay) {
+    a.tape = r->tape;
+    a.tape_stride = r->tape_stride;
+  }
+  a.traj_q = nullptr;   // the chain-0 capture is ignored (the reference never fills it for NUTS)
+  a.n_save = 0;
+  return hip_status(hmc::launch_glm_nuts(logit_args(&d, a), m->family, replay, (hipStream_t)stream), what);
 }
 
 hmc_status hmc_rng_normals(uint64_t seed, int64_t chain0, int64_t n, int32_t iteration, int32_t npairs, double* out,

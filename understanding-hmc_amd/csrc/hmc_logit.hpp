@@ -1,4 +1,5 @@
-// hmc_logit.hpp — argument block and launchers of the logistic-regression kernels (hmc_logit.hip).
+// hmc_logit.hpp — argument block and launchers of the generalized-linear-model kernels: the
+// Random-trajectory kernels (hmc_logit.hip) and the NUTS kernel (hmc_glm_nuts.hip).
 #pragma once
 #include "hmc_internal.hpp"
 
@@ -12,7 +13,7 @@ struct LogitArgs {
   int nrows;               // data rows n, 1 .. HMC_LOGIT_MAX_N
   int64_t ldx;             // row stride of X in doubles, >= D
   const double* X;         // [n][ldx]
-  const double* y;         // [n] 0.0 / 1.0
+  const double* y;         // [n] 0.0 / 1.0 (Bernoulli), counts (Poisson)
   const double* pprec;     // [D] 1 / prior variance
   const double* row_p;     // row-wise entries: [n][D] inputs ...
   const double* row_q;
@@ -21,8 +22,16 @@ struct LogitArgs {
   double* row_E;           // [n] (energy)
 };
 
-hipError_t launch_logit_init(const LogitArgs& x, bool replay, hipStream_t s);
-hipError_t launch_logit_iters(const LogitArgs& x, bool replay, hipStream_t s);
-hipError_t launch_logit_rows(const LogitArgs& x, bool leapfrog, hipStream_t s);
+// family: HMC_GLM_BERNOULLI (the logistic target) or HMC_GLM_POISSON; a template parameter of the
+// kernels, so it is no part of the argument block.
+hipError_t launch_logit_init(const LogitArgs& x, int family, bool replay, hipStream_t s);
+hipError_t launch_logit_iters(const LogitArgs& x, int family, bool replay, hipStream_t s);
+hipError_t launch_logit_rows(const LogitArgs& x, int family, bool leapfrog, hipStream_t s);
+
+// NUTS on a GLM target (hmc_glm_nuts.hip): one wave owns a tile of 16 chains for the whole launch;
+// a.ws is the tile-interleaved workspace of glm_nuts_ws_doubles(n, D, d_max) doubles (the tree
+// vectors, then one replay-tape cursor per chain), a.tape / a.tape_stride the replay tape.
+int64_t glm_nuts_ws_doubles(int64_t n, int D, int d_max);   // 0: unsupported D
+hipError_t launch_glm_nuts(const LogitArgs& x, int family, bool replay, hipStream_t s);
 
 }  // namespace hmc

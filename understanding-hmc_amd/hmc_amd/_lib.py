@@ -19,6 +19,7 @@ NCOUNTERS = 9
 COUNTER_SLOTS = 4096   # include/hmc.h HMC_COUNTER_SLOTS: counters buffer is [slots][NCOUNTERS]
 MIX_MAX_COMPONENTS, MIX_MAX_D = 8, 512   # include/hmc.h HMC_MIX_MAX_COMPONENTS, HMC_MIX_MAX_D
 LOGIT_MAX_D, LOGIT_MAX_N = 128, 1 << 20   # include/hmc.h HMC_LOGIT_MAX_D, HMC_LOGIT_MAX_N
+HMC_GLM_BERNOULLI, HMC_GLM_POISSON = 0, 1   # include/hmc.h hmc_glm.family
 
 c_dp = ctypes.c_void_p  # device pointers are passed as integers (torch data_ptr())
 
@@ -63,6 +64,12 @@ class Logistic(ctypes.Structure):
     """hmc_logistic: design matrix, labels and prior precisions (device pointers)."""
     _fields_ = [("D", ctypes.c_int32), ("n", ctypes.c_int32), ("ldx", ctypes.c_int64), ("X", c_dp), ("y", c_dp),
                 ("prior_prec", c_dp)]
+
+
+class GLM(ctypes.Structure):
+    """hmc_glm: hmc_logistic's data plus the family (device pointers)."""
+    _fields_ = [("D", ctypes.c_int32), ("n", ctypes.c_int32), ("ldx", ctypes.c_int64), ("X", c_dp), ("y", c_dp),
+                ("prior_prec", c_dp), ("family", ctypes.c_int32)]
 
 
 # Exported symbols (tests check every one of these is present; keep in sync with include/hmc.h)
@@ -121,6 +128,17 @@ SYMBOLS = {
                                           c_dp, c_dp, c_dp, c_dp]),
     "hmc_logit_energy": (ctypes.c_int, [ctypes.POINTER(Logistic), ctypes.POINTER(Kinetic), ctypes.c_int64, c_dp, c_dp,
                                         c_dp, c_dp]),
+    "hmc_glm_chain_init": (ctypes.c_int, [ctypes.POINTER(GLM), ctypes.POINTER(Kinetic), ctypes.POINTER(Schedule),
+                                          ctypes.POINTER(Replay), c_dp, ctypes.POINTER(State), c_dp]),
+    "hmc_glm_random_iters": (ctypes.c_int, [ctypes.POINTER(GLM), ctypes.POINTER(Kinetic), ctypes.POINTER(Schedule),
+                                            ctypes.POINTER(Replay), ctypes.POINTER(State), c_dp]),
+    "hmc_glm_leapfrog": (ctypes.c_int, [ctypes.POINTER(GLM), ctypes.POINTER(Kinetic), ctypes.c_int64, c_dp, c_dp,
+                                        c_dp, c_dp, c_dp]),
+    "hmc_glm_energy": (ctypes.c_int, [ctypes.POINTER(GLM), ctypes.POINTER(Kinetic), ctypes.c_int64, c_dp, c_dp,
+                                      c_dp, c_dp]),
+    "hmc_glm_nuts_workspace_size": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),
+    "hmc_glm_nuts_iters": (ctypes.c_int, [ctypes.POINTER(GLM), ctypes.POINTER(Kinetic), ctypes.POINTER(Schedule),
+                                          ctypes.POINTER(Replay), ctypes.POINTER(State), c_dp, ctypes.c_int64, c_dp]),
     "hmc_rng_normals": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                        ctypes.c_int32, c_dp, c_dp]),
     "hmc_philox": (ctypes.c_int, [ctypes.c_uint32] * 6 + [ctypes.c_int64, c_dp, c_dp]),

@@ -432,6 +432,70 @@ class LogisticEngine(_KernelTargetEngine):
         return (t.X, t.y, t.prior_prec)
 
 
+class GLMEngine(_KernelTargetEngine):
+    """Chain batch of the Random-trajectory sampler on a GLMTarget (hmc_glm_chain_init /
+    hmc_glm_random_iters: the logistic kernels of csrc/hmc_logit.hip with the family as a template
+    parameter).  LogisticEngine's limits: diagonal cov_p only, D <= 128, n <= 2^20; `fp_mode` is
+    accepted and changes nothing.  A checkpoint fingerprints the data and the family."""
+
+    _init_entry, _run_entry, _what = "hmc_glm_chain_init", "hmc_glm_random_iters", "GLM"
+
+    @classmethod
+    def check_supported(cls, target, cov_p):
+        """NotImplementedError, before anything touches the device, for what the kernels do not take."""
+        if target.D > H.LOGIT_MAX_D or target.n > H.LOGIT_MAX_N:
+            raise NotImplementedError("GLM kernels: D=%d, n=%d (D <= %d, n <= %d)"
+                                      % (target.D, target.n, H.LOGIT_MAX_D, H.LOGIT_MAX_N))
+        cls._check_diag_mass(cov_p)
+
+    def _descriptors(self, target, cov_p, dt, dense):
+        self.check_supported(target, cov_p)
+        # X as it is, row-major with ldx = D: the kernel clamps its reads to [n][D]
+        self._data = [_dev(a, self.device) for a in (target.X, target.y, target.prior_prec)]
+        self._kinetic(cov_p, dt)
+        self.T = H.GLM(self.D, target.n, self.D, *[H.ptr(x) for x in self._data], target.family_id)
+        return None
+
+    def _target_arrays(self):
+        t = self.t
+        return (t.X, t.y, t.prior_prec, np.float64(t.family_id))
+
+
+class GLMNutsEngine(GLMEngine):
+    """Chain batch of the No-U-Turn sampler on a GLMTarget (hmc_glm_nuts_iters, csrc/hmc_glm_nuts.hip:
+    one wave steps a tile of 16 chains, each its own tree).  NutsEngine's surface: `d_max`, `on_dmax`,
+    `set_replay(p0, P, tape)`, `run(it0, it1)`; the workspace (tree vectors of every chain, then the
+    replay-tape cursors) is allocated zeroed from the size query and stays on the device.  `init()`
+    is GLMEngine's (hmc_glm_chain_init serves both samplers)."""
+
+    def __init__(self, target, n_chains, n_iter, warm_up, thin, d_max, dt, cov_p=None, rng="philox", seed=0,
+                 fp_mode="fast", chain_offset=0, store_chain=True, store_energy=True, on_dmax="raise",
+                 device=None, iters_per_call=None):
+        super().__init__(target, n_chains, n_iter, warm_up, thin, 5, 20, dt, cov_p=cov_p, rng=rng, seed=seed,
+                         fp_mode=fp_mode, chain_offset=chain_offset, store_chain=store_chain,
+                         store_energy=store_energy, n_save=0, device=device)
+        assert on_dmax in ("raise", "break")
+        self.d_max = int(d_max)
+        self.on_dmax = 0 if on_dmax == "raise" else 1
+        nbytes = H.lib().hmc_glm_nuts_workspace_size(self.D, self.N, self.d_max)
+        if nbytes <= 0 and self.N > 0:
+            raise NotImplementedError("GLM NUTS kernel: d_max=%d not supported (1 <= d_max <= 30)" % self.d_max)
+        self.ws = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=self.device)
+
+    def set_replay(self, p0, P, tape):
+        """Host-replayed draws: p0 (N,D), p (N,Niter,D), tape (N,T) directions/uniforms in order."""
+        dev = self.device
+        tape = np.ascontiguousarray(tape, dtype=np.float64)
+        self._streams = [_dev(p0, dev), _dev(P, dev), _dev(tape, dev)]
+        self._replay = H.Replay(H.ptr(self._streams[0]), H.ptr(self._streams[1]), None, None,
+                                H.ptr(self._streams[2]), tape.shape[1])
+
+    def run(self, it0, it1):
+        """Iterations [it0, it1) of every chain in one launch."""
+        H.check(H.lib().hmc_glm_nuts_iters(self.T, self.K, self.schedule(it0, it1), self._replay, self.S,
+                                           H.ptr(self.ws), self.ws.numel() * 8, self.stream()), "hmc_glm_nuts_iters")
+
+
 class NutsEngine(RandomEngine):
     """Chain batch of the No-U-Turn sampler (samplers.py:495-808) on the dense-precision
     MFMA kernel (hmc_nuts_iters).  Diagonal targets are passed as dense precisions.

@@ -25,8 +25,8 @@ import torch
 
 from . import _lib as H
 from .diagnostics import StreamingDiagnostics
-from .engine import LogisticEngine, MixtureEngine, NutsEngine, RandomEngine
-from .target import LogisticTarget, MixtureTarget, MVNTarget, probe_closures  # noqa: F401
+from .engine import GLMEngine, GLMNutsEngine, LogisticEngine, MixtureEngine, NutsEngine, RandomEngine
+from .target import GLMTarget, LogisticTarget, MixtureTarget, MVNTarget, probe_closures  # noqa: F401
 from . import utils as U
 
 
@@ -44,11 +44,19 @@ def _logistic_descriptor(t, up):
     return H.Logistic(t.D, t.n, t.D, *[H.ptr(x) for x in keep]), keep
 
 
+def _glm_descriptor(t, up):
+    keep = [up(a) for a in (t.X, t.y, t.prior_prec)]
+    return H.GLM(t.D, t.n, t.D, *[H.ptr(x) for x in keep], t.family_id), keep
+
+
 # Targets that are not MVN and have kernels of their own: (name, engine, device descriptor for the
-# row-wise calls, leapfrog entry, energy entry).  Random sampler and a diagonal cov_p only.
+# row-wise calls, leapfrog entry, energy entry, NUTS engine or None).  A diagonal cov_p only; the
+# Random sampler, and NUTS where the target has a NUTS engine.
 _KERNEL_TARGETS = {
-    MixtureTarget: ("mixture", MixtureEngine, _mixture_descriptor, "hmc_mix_leapfrog", "hmc_mix_energy"),
-    LogisticTarget: ("logistic", LogisticEngine, _logistic_descriptor, "hmc_logit_leapfrog", "hmc_logit_energy"),
+    MixtureTarget: ("mixture", MixtureEngine, _mixture_descriptor, "hmc_mix_leapfrog", "hmc_mix_energy", None),
+    LogisticTarget: ("logistic", LogisticEngine, _logistic_descriptor, "hmc_logit_leapfrog", "hmc_logit_energy",
+                     None),
+    GLMTarget: ("GLM", GLMEngine, _glm_descriptor, "hmc_glm_leapfrog", "hmc_glm_energy", GLMNutsEngine),
 }
 
 
@@ -104,8 +112,10 @@ class HMC_sampler(sampler):
                  before any launch; fp_mode changes nothing for it).  Or a LogisticTarget (design
                  matrix X (n, D), labels y, normal prior; sampler_type="Random", a diagonal cov_p,
                  D <= 128, n <= 2^20: anything else raises NotImplementedError here; fp_mode changes
-                 nothing for it either).  With a target, V / dVdq may be None: they are set to the
-                 target's host methods
+                 nothing for it either).  Or a GLMTarget (the logistic target's data and limits plus a
+                 family, "poisson" or "bernoulli"): sampler_type="Random" or "NUTS", the one target
+                 with kernels of its own that NUTS runs on.  With a target, V / dVdq may be None:
+                 they are set to the target's host methods
       rng      : "replay" | "philox"
       seed     : Philox key (rng="philox")
       fp_mode  : "exact" (reference rounding, no FMA) | "fast" (FMA-contracted integrator)
@@ -176,7 +186,7 @@ class HMC_sampler(sampler):
         if self._kernel_target:
             name, engine = self._kernel_target[:2]
             assert target.D == self.D
-            if self.sampler_type == "NUTS":
+            if self.sampler_type == "NUTS" and self._kernel_target[5] is None:
                 raise NotImplementedError("NUTS on a %s target is not supported (sampler_type='Random')" % name)
             engine.check_supported(target, self.cov_p)
         self.n_leapfrog = 0
@@ -406,12 +416,14 @@ class HMC_sampler(sampler):
                           "from np.random (reproducible, statistically equivalent, not the reference's "
                           "draws)", UserWarning, stacklevel=2)
             rng, seed = "philox", int(np.random.randint(0, 2 ** 62, dtype=np.int64))
-        eng = NutsEngine(self.target(), self.Nchain, self.Niter, self.warm_up_num, self.thin_rate, self.d_max,
-                         self.dt, cov_p=self.cov_p, rng=rng, seed=seed, fp_mode=self.fp_mode,
-                         chain_offset=self.chain_offset, store_chain=self.store_chain, on_dmax=on_dmax,
-                         device=self.device,
-                         iters_per_call=(self.iters_per_launch or self.Niter) if self.store_chain
-                         else (self.iters_per_launch or 20))                  # (_run's launch sizes)
+        # the target's own NUTS kernel (hmc_glm_nuts.hip) or the MVN kernels
+        engine = self._kernel_target[5] if self._kernel_target else NutsEngine
+        eng = engine(self.target(), self.Nchain, self.Niter, self.warm_up_num, self.thin_rate, self.d_max,
+                     self.dt, cov_p=self.cov_p, rng=rng, seed=seed, fp_mode=self.fp_mode,
+                     chain_offset=self.chain_offset, store_chain=self.store_chain, on_dmax=on_dmax,
+                     device=self.device,
+                     iters_per_call=(self.iters_per_launch or self.Niter) if self.store_chain
+                     else (self.iters_per_launch or 20))                      # (_run's launch sizes)
         if rng == "replay":
             eng.set_replay(*tape)
         t0 = time.time()

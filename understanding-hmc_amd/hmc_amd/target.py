@@ -179,6 +179,81 @@ class LogisticTarget:
         return (sigma - self.y) @ self.X + q * self.prior_prec
 
 
+class GLMTarget:
+    """Posterior of the coefficients q of a generalized linear model: design matrix X (n, D),
+    responses y (n,), linear predictor z = X q, and an independent zero-mean normal prior with
+    variances prior_var (scalar or (D,)).  No normalising constants:
+        family="poisson"    (log link, y = 0, 1, 2, ...)
+            V(q)  = sum_j [exp(z_j) - y_j z_j] + 0.5 sum_d q_d^2 / prior_var_d
+            dV/dq = X^T (exp(z) - y) + q / prior_var
+            exp(z) overflows to inf from z ~ 709.78 on: V is then inf, which the samplers treat as any
+            non-finite energy (Random rejects the proposal, NUTS counts the sub-tree unstable)
+        family="bernoulli"  (logit link, y in {0, 1}): LogisticTarget's V and dV/dq, the same posterior
+    Both samplers run on it: Random through csrc/hmc_logit.hip (the family is a template parameter of
+    the logistic kernels), NUTS through csrc/hmc_glm_nuts.hip.  The host V / dVdq below serve
+    HMC_sampler.V / .dVdq and the plots, for one row or for batched (..., D) rows.  `q0` is the prior
+    mean, zeros(D)."""
+
+    diagonal = True
+    FAMILIES = {"bernoulli": 0, "poisson": 1}        # include/hmc.h HMC_GLM_BERNOULLI, HMC_GLM_POISSON
+
+    def __init__(self, X, y, family="poisson", prior_var=1.0):
+        if family not in self.FAMILIES:
+            raise AssertionError("GLMTarget family must be one of %s" % sorted(self.FAMILIES))
+        self.family = family
+        self.family_id = self.FAMILIES[family]
+        self.X = np.ascontiguousarray(X, dtype=np.float64)
+        self.y = np.ascontiguousarray(y, dtype=np.float64)
+        if self.X.ndim != 2 or self.X.shape[0] < 1 or self.X.shape[1] < 1:
+            raise AssertionError("GLMTarget takes X (n, D) with n >= 1 and D >= 1")
+        if self.y.shape != (self.X.shape[0],):
+            raise AssertionError("GLMTarget takes y (n,) with one response per row of X")
+        if family == "bernoulli":
+            if not np.all((self.y == 0.0) | (self.y == 1.0)):
+                raise AssertionError("bernoulli responses must be 0 or 1")
+        elif not (np.all(np.isfinite(self.y)) and np.all(self.y >= 0.0) and np.all(self.y == np.floor(self.y))):
+            raise AssertionError("poisson responses must be non-negative integers")
+        pv = np.asarray(prior_var, dtype=np.float64)
+        if pv.ndim == 0:
+            pv = np.full(self.D, float(pv))
+        self.prior_var = np.ascontiguousarray(pv)
+        if self.prior_var.shape != (self.D,):
+            raise AssertionError("prior_var must be a scalar or (D,)")
+        if not np.all(self.prior_var > 0):
+            raise AssertionError("prior_var must be positive")
+        self.prior_prec = 1.0 / self.prior_var
+        self.q0 = np.zeros(self.D)
+
+    @property
+    def D(self):
+        return self.X.shape[1]
+
+    @property
+    def n(self):
+        return self.X.shape[0]
+
+    def V(self, q):
+        q = np.asarray(q, dtype=np.float64)
+        z = q @ self.X.T                                            # (..., n)
+        with np.errstate(over="ignore"):
+            if self.family == "poisson":
+                nll = np.exp(z)                                     # inf past ~709.78: V = inf
+            else:
+                nll = np.maximum(z, 0.0) + np.log1p(np.exp(-np.abs(z)))
+        return np.sum(nll - self.y * z, axis=-1) + 0.5 * np.sum(q * q * self.prior_prec, axis=-1)
+
+    def dVdq(self, q):
+        q = np.asarray(q, dtype=np.float64)
+        z = q @ self.X.T
+        with np.errstate(over="ignore"):
+            if self.family == "poisson":
+                mean = np.exp(z)
+            else:
+                t = np.exp(-np.abs(z))
+                mean = np.where(z >= 0, 1.0, t) / (1.0 + t)
+        return (mean - self.y) @ self.X + q * self.prior_prec
+
+
 def probe_closures(D, V, dVdq, n_check=4, rtol=1e-9, seed=12345):
     """Recover an MVNTarget from the reference-style closures by affine probing."""
     z = np.zeros(D)
