@@ -435,6 +435,56 @@ int64_t hmc_glm_nuts_workspace_size(int32_t D, int64_t n_chains, int32_t d_max);
 hmc_status hmc_glm_nuts_iters(const hmc_glm* m, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
                               hmc_state* st, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------- step-size adaptation (GLM)
+ * On a posterior defined by data nobody knows the curvature in advance, so the two GLM samplers can
+ * find their own step during warm-up: every chain carries a multiplier s of the caller's step (the
+ * effective step of dimension d is s dt_d, for a scalar dt or a dt_vec; minv is unchanged) and
+ * adapts it by the Nesterov dual averaging of Hoffman & Gelman 2014, section 3.2.  Per chain, so a
+ * chain's results still depend on nothing but its global chain id: the invariances of the plain
+ * entries (tile column, neighbours, launch split, sharding with chain_offset) hold here too.
+ *
+ * state: [n_chains][HMC_ADAPT_STRIDE] doubles, caller-owned, carried between launches, indexed like
+ *   hmc_state.q (row i = chain chain_offset + i of this call):
+ *     0 log_s  1 log_s_bar  2 H_bar  3 m  4 mu  5 sum_alpha_adapt  6 sum_alpha_after  7 n_after
+ *   hmc_adapt_init writes log_s = log_s_bar = mu = log(s0[i]) (s0 NULL: 0, i.e. s = 1), the rest 0.
+ * An iteration i < adapt_end runs at s = exp(log_s) and updates the state at its end from its
+ *   acceptance statistic alpha (slot 5 += alpha):
+ *     m += 1;  H_bar = (1 - 1/(m + t0)) H_bar + (delta - alpha)/(m + t0)
+ *     log_s = clamp(mu - sqrt(m)/gamma H_bar, mu - 20 ln 2, mu + 20 ln 2)
+ *     eta = m^-kappa;  log_s_bar = eta log_s + (1 - eta) log_s_bar
+ *   An iteration i >= adapt_end runs at exp(log_s_bar) (exp(log_s) while m == 0) and only adds
+ *   alpha to slot 6 and 1 to slot 7.  exp(log_s_bar) is the adapted multiplier to report.
+ * mu = log(s0), not Stan's log(10 s0): the caller's step is the point the iterates shrink to.  The
+ *   first update moves s by at most e^(20 * 0.8 / 11) ~ 4.3 either way, and the iteration after a
+ *   perfect acceptance runs at e^(20 * 0.2 / 11) ~ 1.44 s0.  With log(10 s0) it runs at 14.4 s0,
+ *   which overflows exp(z) of the Poisson family; the energies turn NaN, NaN passes the reference's
+ *   |E - E_init| > 1000 guard, and the chain never recovers.
+ * alpha: Random: min(1, exp(-dE)) of the iteration's Metropolis test.  NUTS: the mean over every
+ *   leapfrog point of the iteration's tree (every sub-tree, also a rejected one, also the point that
+ *   trips the unstable guard) of min(1, exp(E_init - E_point)).  A point whose energy (or whose
+ *   energy difference) is not finite contributes 0.
+ * delta in (0, 1) is the target of the mean alpha; gamma = 0.05, t0 = 10, kappa = 0.75 are the
+ *   paper's values.
+ * With every s = 1 and adapt_end <= iter_begin the _adapt entries compute what the plain entries
+ * compute, bit for bit (1.0 x is exact); the plain entries launch the kernels they always did.
+ * HMC_EINVAL: a NULL adapt block or state, delta outside (0, 1), gamma, t0 or kappa <= 0 (or NaN);
+ * everything else as the plain entry of the same name. */
+enum { HMC_ADAPT_STRIDE = 8 };
+typedef struct hmc_adapt {
+  double* state;              /* [n_chains][HMC_ADAPT_STRIDE]                                */
+  int32_t adapt_end;          /* iterations i < adapt_end adapt (0: none)                    */
+  double delta, gamma, t0, kappa;
+} hmc_adapt;                  /* 48 bytes: offsets 0, 8, 16, 24, 32, 40                      */
+
+hmc_status hmc_adapt_init(double* state, int64_t n_chains, const double* s0 /* [n_chains] > 0, or NULL */,
+                          void* stream);
+hmc_status hmc_glm_random_iters_adapt(const hmc_glm* m, const hmc_kinetic* k, const hmc_schedule* s,
+                                      const hmc_replay* r /* NULL for Philox */, hmc_state* st,
+                                      const hmc_adapt* ad, void* stream);
+hmc_status hmc_glm_nuts_iters_adapt(const hmc_glm* m, const hmc_kinetic* k, const hmc_schedule* s,
+                                    const hmc_replay* r, hmc_state* st, void* workspace, int64_t workspace_bytes,
+                                    const hmc_adapt* ad, void* stream);
+
 /* The standard normals the Philox mode draws for (chain, iteration): out[n][2*npairs].
  * Debug/verification entry (statistical tests of the in-kernel generator). */
 hmc_status hmc_rng_normals(uint64_t seed, int64_t chain0, int64_t n, int32_t iteration,

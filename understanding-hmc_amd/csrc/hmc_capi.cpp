@@ -726,8 +726,21 @@ hmc_status glm_chain_init(const hmc_logistic* m, int family, const hmc_kinetic* 
   return hip_status(hmc::launch_logit_init(logit_args(m, a), family, replay, (hipStream_t)stream), what);
 }
 
+// The _adapt entries' own argument: HMC_EINVAL for a null block or state, a delta outside (0, 1),
+// a non-positive (or NaN) gamma, t0 or kappa.
+hmc_status check_adapt(const hmc_adapt* ad, const char* what) {
+  if (!ad || !ad->state) return fail(HMC_EINVAL, "%s: null adapt block / state", what);
+  if (!(ad->delta > 0.0 && ad->delta < 1.0))
+    return fail(HMC_EINVAL, "%s: delta=%g, the target acceptance statistic lies in (0, 1)", what, ad->delta);
+  if (!(ad->gamma > 0.0) || !(ad->t0 > 0.0) || !(ad->kappa > 0.0))
+    return fail(HMC_EINVAL, "%s: gamma=%g, t0=%g, kappa=%g must be positive", what, ad->gamma, ad->t0, ad->kappa);
+  return HMC_OK;
+}
+
+// ad: NULL for the plain entry; the _adapt entry has checked it (check_adapt)
 hmc_status glm_random_iters(const hmc_logistic* m, int family, const hmc_kinetic* k, const hmc_schedule* s,
-                            const hmc_replay* r, hmc_state* st, void* stream, const char* what) {
+                            const hmc_replay* r, hmc_state* st, void* stream, const char* what,
+                            const hmc_adapt* ad = nullptr) {
   if (hmc_status e = check_logistic(m, k, what)) return e;
   const hmc_target t = logit_shape(m);
   if (hmc_status e = check_schedule(&t, k, s, true)) return e;
@@ -744,7 +757,7 @@ hmc_status glm_random_iters(const hmc_logistic* m, int family, const hmc_kinetic
     return fail(HMC_EINVAL, "traj_stride must be >= L_high");
   const hmc::Layout lay{0, 0, 0, (m->D + 1) / 2};
   const hmc::RandArgs a = rand_args(&t, k, s, replay ? r : nullptr, st, lay);
-  return hip_status(hmc::launch_logit_iters(logit_args(m, a), family, replay, (hipStream_t)stream), what);
+  return hip_status(hmc::launch_logit_iters(logit_args(m, a), family, replay, (hipStream_t)stream, ad), what);
 }
 
 hmc_status glm_leapfrog(const hmc_logistic* m, int family, const hmc_kinetic* k, int64_t n, const double* p,
@@ -838,9 +851,12 @@ int64_t hmc_glm_nuts_workspace_size(int32_t D, int64_t n_chains, int32_t d_max) 
   return hmc::glm_nuts_ws_doubles(n_chains, D, d_max) * (int64_t)sizeof(double);
 }
 
-hmc_status hmc_glm_nuts_iters(const hmc_glm* m, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
-                              hmc_state* st, void* workspace, int64_t workspace_bytes, void* stream) {
-  const char* what = "hmc_glm_nuts_iters";
+namespace {
+
+// ad: NULL for the plain entry; the _adapt entry has checked it (check_adapt)
+hmc_status glm_nuts_iters(const hmc_glm* m, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
+                          hmc_state* st, void* workspace, int64_t workspace_bytes, void* stream, const char* what,
+                          const hmc_adapt* ad) {
   hmc_logistic d;
   if (hmc_status e = glm_data(m, what, &d)) return e;
   if (hmc_status e = check_logistic(&d, k, what)) return e;
@@ -874,7 +890,37 @@ hmc_status hmc_glm_nuts_iters(const hmc_glm* m, const hmc_kinetic* k, const hmc_
   }
   a.traj_q = nullptr;   // the chain-0 capture is ignored (the reference never fills it for NUTS)
   a.n_save = 0;
-  return hip_status(hmc::launch_glm_nuts(logit_args(&d, a), m->family, replay, (hipStream_t)stream), what);
+  return hip_status(hmc::launch_glm_nuts(logit_args(&d, a), m->family, replay, (hipStream_t)stream, ad), what);
+}
+
+}  // namespace
+
+hmc_status hmc_glm_nuts_iters(const hmc_glm* m, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
+                              hmc_state* st, void* workspace, int64_t workspace_bytes, void* stream) {
+  return glm_nuts_iters(m, k, s, r, st, workspace, workspace_bytes, stream, "hmc_glm_nuts_iters", nullptr);
+}
+
+// ---------------------------------------------------------------- step-size adaptation (GLM)
+hmc_status hmc_adapt_init(double* state, int64_t n_chains, const double* s0, void* stream) {
+  if (n_chains < 0 || (n_chains > 0 && !state)) return fail(HMC_EINVAL, "hmc_adapt_init: null state / n_chains < 0");
+  return hip_status(hmc::launch_adapt_init(state, n_chains, s0, (hipStream_t)stream), "hmc_adapt_init");
+}
+
+hmc_status hmc_glm_random_iters_adapt(const hmc_glm* m, const hmc_kinetic* k, const hmc_schedule* s,
+                                      const hmc_replay* r, hmc_state* st, const hmc_adapt* ad, void* stream) {
+  const char* what = "hmc_glm_random_iters_adapt";
+  if (hmc_status e = check_adapt(ad, what)) return e;
+  hmc_logistic d;
+  if (hmc_status e = glm_data(m, what, &d)) return e;
+  return glm_random_iters(&d, m->family, k, s, r, st, stream, what, ad);
+}
+
+hmc_status hmc_glm_nuts_iters_adapt(const hmc_glm* m, const hmc_kinetic* k, const hmc_schedule* s,
+                                    const hmc_replay* r, hmc_state* st, void* workspace, int64_t workspace_bytes,
+                                    const hmc_adapt* ad, void* stream) {
+  const char* what = "hmc_glm_nuts_iters_adapt";
+  if (hmc_status e = check_adapt(ad, what)) return e;
+  return glm_nuts_iters(m, k, s, r, st, workspace, workspace_bytes, stream, what, ad);
 }
 
 hmc_status hmc_rng_normals(uint64_t seed, int64_t chain0, int64_t n, int32_t iteration, int32_t npairs, double* out,

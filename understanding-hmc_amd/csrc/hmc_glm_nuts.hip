@@ -110,9 +110,17 @@ __device__ __forceinline__ void ws_dots(const TileWS& w, int v, int vl, const do
   }
 }
 
-template <int FAMILY, int MT, bool REPLAY>
+// ADAPT: every chain runs at its own multiple s of the step and adapts it during warm-up
+// (hmc_adapt.hpp).  The lane holds its chain's state for the launch; the acceptance statistic is
+// accumulated where a new point's energy is formed (step 5) and the update runs in the iteration-end
+// transition, all on per-lane scalars.  With ADAPT = false none of it is compiled and the kernel
+// takes the plain argument block: those instances are the code they were before the ADAPT form.
+template <bool ADAPT>
+using NutsKernelArgs = std::conditional_t<ADAPT, LogitAdaptArgs, LogitArgs>;
+
+template <int FAMILY, int MT, bool REPLAY, bool ADAPT>
 __global__ __launch_bounds__(64 * kLogitWaves) __attribute__((amdgpu_waves_per_eu(kItersWaves<MT>, kItersWaves<MT>)))
-void k_glm_nuts(LogitArgs x) {
+void k_glm_nuts(NutsKernelArgs<ADAPT> x) {
   constexpr int M = 4 * MT;
   const RandArgs& a = x.a;
   __shared__ DimTable sd;
@@ -141,6 +149,19 @@ void k_glm_nuts(LogitArgs x) {
   int d = 0, k = 0, Lsub = 1, udir = 0, ndraw = 0, old = 0;
   double E_init = 0.0, E_max_now = 0.0, E_max_old = 0.0, pi_new = 1.0, pi_old = 1.0;   // TreeWeights
   unsigned long long n_lf = 0, n_unst = 0, n_dmax = 0, n_tape = 0, n_steps = 0;
+  // ADAPT: the chain's state, the multiplier of the current iteration, the sum of the point
+  // statistics of its tree and their number
+  hmc_adapt ax{};
+  AdaptParams adp{};
+  AdaptState ad{};
+  double s = 1.0, alpha_sum = 0.0;
+  int alpha_n = 0;
+  if constexpr (ADAPT) {
+    ax = x.ad;
+    adp = AdaptParams{ax.delta, ax.gamma, ax.t0, ax.kappa};
+    ad = t.live ? adapt_load(ax.state + t.c * HMC_ADAPT_STRIDE) : adapt_initial(1.0);
+    s = adapt_scale(ad, it < ax.adapt_end);
+  }
 
   auto draw = [&](bool direction) {                     // next random number of this chain (reference order)
     if constexpr (REPLAY) return NutsDraws::tape(tpos, a, n_tape, t.c, direction);
@@ -159,6 +180,12 @@ void k_glm_nuts(LogitArgs x) {
           if (dim_ok(t, m)) rowp[t.h + 4 * m] = q[m];
       }
       Eprev = E_init;                                   // :787
+      if constexpr (ADAPT) {                            // every tree has a first point: alpha_n >= 1
+        adapt_iteration(ad, adp, it < ax.adapt_end, alpha_sum / (double)alpha_n);
+        s = adapt_scale(ad, it + 1 < ax.adapt_end);
+        alpha_sum = 0.0;
+        alpha_n = 0;
+      }
       ++it;
       state = it < a.it1 ? S_START : S_DONE;
     }
@@ -179,9 +206,9 @@ void k_glm_nuts(LogitArgs x) {
 
     // ================= 2.-4. one leapfrog for every chain inside a sub-tree (:612-614, :639)
     const bool act = state == S_TREE;
-    if (act) kick_drift<MT>(t, sd, g, p, q);
+    if (act) kick_drift<MT, ADAPT>(t, sd, g, p, q, s);
     const double vp = logit_grad<FAMILY, MT>(x, t, sd, q, g);
-    if (act) kick<MT>(t, sd, g, p);
+    if (act) kick<MT, ADAPT>(t, sd, g, p, s);
     const double E = chain_sum4(vp + kinetic_part<MT>(t, sd, p));   // :569 / :618 / :643
     if (act && t.h == 0) ++n_lf;
     ++n_steps;
@@ -212,6 +239,12 @@ void k_glm_nuts(LogitArgs x) {
     bool reject = false, sub_end = false;
     const int mpt = k + 1;                              // point number within the sub-tree
     const bool first = act && k == 0, later = act && k > 0;
+    if constexpr (ADAPT) {
+      if (act) {                                        // every point whose energy is evaluated
+        alpha_sum += adapt_alpha(E - E_init, E);
+        ++alpha_n;
+      }
+    }
     if (first) {                                        // first point (:617-626)
       ws_store<M>(w, V_LIVE, 1 - old, q);               // live_point_new
       E_max_now = E;
@@ -301,6 +334,7 @@ void k_glm_nuts(LogitArgs x) {
   if (t.live && t.h == 0) {
     a.Eprev[t.c] = Eprev;
     if constexpr (REPLAY) *tcur = tpos;
+    if constexpr (ADAPT) adapt_store(ax.state + t.c * HMC_ADAPT_STRIDE, ad);
   }
   n_lf = wave_sum_u64(n_lf);
   n_unst = wave_sum_u64(n_unst);
@@ -310,10 +344,16 @@ void k_glm_nuts(LogitArgs x) {
 }
 
 template <int FAMILY, int MT>
-hipError_t launch_mt(const LogitArgs& x, bool replay, hipStream_t s) {
+hipError_t launch_mt(const LogitArgs& x, bool replay, const hmc_adapt* ad, hipStream_t s) {
   const dim3 grid((unsigned)((x.a.ntiles + kLogitWaves - 1) / kLogitWaves)), block(64 * kLogitWaves);
-  if (replay) k_glm_nuts<FAMILY, MT, true><<<grid, block, 0, s>>>(x);
-  else k_glm_nuts<FAMILY, MT, false><<<grid, block, 0, s>>>(x);
+  if (ad) {
+    const LogitAdaptArgs xa{x, *ad};
+    if (replay) k_glm_nuts<FAMILY, MT, true, true><<<grid, block, 0, s>>>(xa);
+    else k_glm_nuts<FAMILY, MT, false, true><<<grid, block, 0, s>>>(xa);
+  } else {
+    if (replay) k_glm_nuts<FAMILY, MT, true, false><<<grid, block, 0, s>>>(x);
+    else k_glm_nuts<FAMILY, MT, false, false><<<grid, block, 0, s>>>(x);
+  }
   return hipGetLastError();
 }
 
@@ -325,12 +365,12 @@ int glm_tiles(int D) {
 }
 
 template <int FAMILY>
-hipError_t launch_family(const LogitArgs& x, bool replay, hipStream_t s) {
+hipError_t launch_family(const LogitArgs& x, bool replay, const hmc_adapt* ad, hipStream_t s) {
   switch (glm_tiles(x.a.D)) {
-    case 1: return launch_mt<FAMILY, 1>(x, replay, s);
-    case 2: return launch_mt<FAMILY, 2>(x, replay, s);
-    case 4: return launch_mt<FAMILY, 4>(x, replay, s);
-    case 8: return launch_mt<FAMILY, 8>(x, replay, s);
+    case 1: return launch_mt<FAMILY, 1>(x, replay, ad, s);
+    case 2: return launch_mt<FAMILY, 2>(x, replay, ad, s);
+    case 4: return launch_mt<FAMILY, 4>(x, replay, ad, s);
+    case 8: return launch_mt<FAMILY, 8>(x, replay, ad, s);
   }
   return hipErrorInvalidValue;
 }
@@ -344,13 +384,13 @@ int64_t glm_nuts_ws_doubles(int64_t n, int D, int d_max) {
   return tiles * glm_nuts_nvec(d_max) * (4 * MT) * kWave + tiles * 16;   // vectors, then the tape cursors
 }
 
-hipError_t launch_glm_nuts(const LogitArgs& x0, int family, bool replay, hipStream_t s) {
+hipError_t launch_glm_nuts(const LogitArgs& x0, int family, bool replay, hipStream_t s, const hmc_adapt* ad) {
   LogitArgs x = x0;
   if (x.a.n == 0 || x.a.it1 <= x.a.it0) return hipSuccess;
   x.a.ntiles = (x.a.n + 15) / 16;
   switch (family) {
-    case HMC_GLM_BERNOULLI: return launch_family<HMC_GLM_BERNOULLI>(x, replay, s);
-    case HMC_GLM_POISSON: return launch_family<HMC_GLM_POISSON>(x, replay, s);
+    case HMC_GLM_BERNOULLI: return launch_family<HMC_GLM_BERNOULLI>(x, replay, ad, s);
+    case HMC_GLM_POISSON: return launch_family<HMC_GLM_POISSON>(x, replay, ad, s);
   }
   return hipErrorInvalidValue;
 }

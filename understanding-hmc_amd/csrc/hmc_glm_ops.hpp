@@ -4,6 +4,7 @@
 // half kicks, the kinetic energy, the row loads / stores and the momentum draw.
 // Lane l = (chain c = l & 15, h = l >> 4) owns dims d = h + 4m, m < 4*MT, of chain c.
 #pragma once
+#include "hmc_adapt.hpp"
 #include "hmc_device.hpp"
 #include "hmc_dense_ops.hpp"
 #include "hmc_logit.hpp"
@@ -183,28 +184,38 @@ __device__ __forceinline__ double logit_grad(const LogitArgs& x, const TileLane&
   return vp;
 }
 
+// A table entry that scales with the step (kDt, kHalfKick) under the lane's step multiplier s
+// (hmc_adapt.hpp): one multiply per table read in the ADAPT form, the entry itself otherwise.
+template <bool ADAPT>
+__device__ __forceinline__ double step_entry(double entry, double s) {
+  if constexpr (ADAPT) return s * entry;
+  else return entry;
+}
+
 // First half of samplers.py:831-839: p_half (left in p) and q_new.  Padding dims stay 0.
-template <int MT>
+// ADAPT: the step is s dt_d, with s the multiplier of the lane's chain.
+template <int MT, bool ADAPT = false>
 __device__ __forceinline__ void kick_drift(const TileLane& t, const DimTable& sd, const d4 (&g)[MT],
-                                           double (&p)[4 * MT], double (&q)[4 * MT]) {
+                                           double (&p)[4 * MT], double (&q)[4 * MT], double s = 1.0) {
   const int ho = table_lane(t.h);
 #pragma unroll
   for (int m = 0; m < 4 * MT; ++m) {
     const double gm = dim_ok(t, m) ? gval<MT>(g, m) : 0.0;
-    p[m] = __builtin_fma(-sd[kHalfKick][ho + 4 * m], gm, p[m]);
-    q[m] = __builtin_fma(sd[kDt][ho + 4 * m], p[m], q[m]);
+    p[m] = __builtin_fma(-step_entry<ADAPT>(sd[kHalfKick][ho + 4 * m], s), gm, p[m]);
+    q[m] = __builtin_fma(step_entry<ADAPT>(sd[kDt][ho + 4 * m], s), p[m], q[m]);
     if ((m & 7) == 7) __builtin_amdgcn_sched_barrier(0);     // bound the table reads in flight
   }
 }
 
 // Second half: p_new = p_half - dt (minv g(q_new)) / 2.
-template <int MT>
-__device__ __forceinline__ void kick(const TileLane& t, const DimTable& sd, const d4 (&g)[MT], double (&p)[4 * MT]) {
+template <int MT, bool ADAPT = false>
+__device__ __forceinline__ void kick(const TileLane& t, const DimTable& sd, const d4 (&g)[MT], double (&p)[4 * MT],
+                                     double s = 1.0) {
   const int ho = table_lane(t.h);
 #pragma unroll
   for (int m = 0; m < 4 * MT; ++m) {
     const double gm = dim_ok(t, m) ? gval<MT>(g, m) : 0.0;
-    p[m] = __builtin_fma(-sd[kHalfKick][ho + 4 * m], gm, p[m]);
+    p[m] = __builtin_fma(-step_entry<ADAPT>(sd[kHalfKick][ho + 4 * m], s), gm, p[m]);
   }
 }
 

@@ -73,10 +73,17 @@ __global__ __launch_bounds__(64 * kLogitWaves) void k_logit_init(LogitArgs x) {
 }
 
 // ------------------------------------------------------------------------------------------
-// Iterations [it0, it1) (samplers.py:428-475).
-template <int FAMILY, int MT, bool REPLAY>
+// Iterations [it0, it1) (samplers.py:428-475).  ADAPT: every chain runs at its own multiple s of
+// the step and adapts it during warm-up from min(1, exp(-dE)) of its Metropolis test
+// (hmc_adapt.hpp); the lane holds its chain's state for the launch.  With ADAPT = false none of it
+// is compiled and the kernel takes the plain argument block: those instances are the code they were
+// before the ADAPT form.
+template <bool ADAPT>
+using ItersKernelArgs = std::conditional_t<ADAPT, LogitAdaptArgs, LogitArgs>;
+
+template <int FAMILY, int MT, bool REPLAY, bool ADAPT>
 __global__ __launch_bounds__(64 * kLogitWaves) __attribute__((amdgpu_waves_per_eu(kItersWaves<MT>, kItersWaves<MT>)))
-void k_logit_iters(LogitArgs x) {
+void k_logit_iters(ItersKernelArgs<ADAPT> x) {
   constexpr int M = 4 * MT;
   const RandArgs& a = x.a;
   __shared__ DimTable sd;
@@ -98,6 +105,16 @@ void k_logit_iters(LogitArgs x) {
   // chain-0 trajectory capture (samplers.py:442-452): the wave holding global chain 0 (lane 0)
   const bool cap_wave = a.traj_q && uniform_i((int)(__builtin_amdgcn_readfirstlane((int)(gc & 0xffffffff)) == 0 &&
                                                     __builtin_amdgcn_readfirstlane((int)(gc >> 32)) == 0));
+  hmc_adapt ax{};
+  AdaptParams adp{};
+  AdaptState ad{};
+  double s = 1.0;   // ADAPT: the chain's step multiplier of the current iteration
+  if constexpr (ADAPT) {
+    ax = x.ad;
+    adp = AdaptParams{ax.delta, ax.gamma, ax.t0, ax.kappa};
+    ad = t.live ? adapt_load(ax.state + t.c * HMC_ADAPT_STRIDE) : adapt_initial(1.0);
+    s = adapt_scale(ad, a.it0 < ax.adapt_end);
+  }
 
   for (int it = a.it0; it < a.it1; ++it) {
     draw_momentum<MT, REPLAY, true>(a, t, sd, it, gc, s_ntab, p);          // samplers.py:431
@@ -133,7 +150,7 @@ void k_logit_iters(LogitArgs x) {
     double vp = 0.0, E0 = 0.0;
     for (int l = -1; l < Lmax; ++l) {
       const bool act = l >= 0 && l < L;
-      if (act) kick_drift<MT>(t, sd, g, p, q);
+      if (act) kick_drift<MT, ADAPT>(t, sd, g, p, q, s);
       const double vn = logit_grad<FAMILY, MT>(x, t, sd, q, g);
       if (l < 0) {                                           // uniform
         vp = vn;
@@ -146,7 +163,7 @@ void k_logit_iters(LogitArgs x) {
         continue;
       }
       if (act) {
-        kick<MT>(t, sd, g, p);
+        kick<MT, ADAPT>(t, sd, g, p, s);
         vp = vn;
       }
       if (cap) {
@@ -163,6 +180,10 @@ void k_logit_iters(LogitArgs x) {
     const bool accept = (dE < 0.0) || (lnu < -dE);
     if (accept) store_dims<MT>(qrow, t, q);
     else load_dims<MT>(qrow, t, q);
+    if constexpr (ADAPT) {
+      adapt_iteration(ad, adp, it < ax.adapt_end, adapt_alpha(dE, E1));
+      s = adapt_scale(ad, it + 1 < ax.adapt_end);
+    }
     if (write_row && qcb && row >= a.q_row0) {
       double* rowp = qcb + (row % a.Lq) * a.D;
 #pragma unroll
@@ -186,7 +207,10 @@ void k_logit_iters(LogitArgs x) {
   }
 
   // ---- state write-back and counters (a.q already holds q)
-  if (t.live && t.h == 0) a.Eprev[t.c] = Eprev;
+  if (t.live && t.h == 0) {
+    a.Eprev[t.c] = Eprev;
+    if constexpr (ADAPT) adapt_store(ax.state + t.c * HMC_ADAPT_STRIDE, ad);
+  }
   n_acc = wave_sum_u64(n_acc);
   n_acc_wu = wave_sum_u64(n_acc_wu);
   n_lf = wave_sum_u64(n_lf);
@@ -232,8 +256,9 @@ __global__ __launch_bounds__(64 * kLogitWaves) void k_logit_rows(LogitArgs x) {
   }
 }
 
+// what: 0 init, 1 iterations (ad: NULL the plain kernel, otherwise its ADAPT form), 2 rows
 template <int FAMILY, int MT>
-hipError_t launch_mt(const LogitArgs& x, int what, bool flag, hipStream_t s) {
+hipError_t launch_mt(const LogitArgs& x, int what, bool flag, const hmc_adapt* ad, hipStream_t s) {
   const dim3 grid((unsigned)((x.a.ntiles + kLogitWaves - 1) / kLogitWaves)), block(64 * kLogitWaves);
   switch (what) {
     case 0:
@@ -241,8 +266,14 @@ hipError_t launch_mt(const LogitArgs& x, int what, bool flag, hipStream_t s) {
       else k_logit_init<FAMILY, MT, false><<<grid, block, 0, s>>>(x);
       break;
     case 1:
-      if (flag) k_logit_iters<FAMILY, MT, true><<<grid, block, 0, s>>>(x);
-      else k_logit_iters<FAMILY, MT, false><<<grid, block, 0, s>>>(x);
+      if (ad) {
+        const LogitAdaptArgs xa{x, *ad};
+        if (flag) k_logit_iters<FAMILY, MT, true, true><<<grid, block, 0, s>>>(xa);
+        else k_logit_iters<FAMILY, MT, false, true><<<grid, block, 0, s>>>(xa);
+      } else {
+        if (flag) k_logit_iters<FAMILY, MT, true, false><<<grid, block, 0, s>>>(x);
+        else k_logit_iters<FAMILY, MT, false, false><<<grid, block, 0, s>>>(x);
+      }
       break;
     default:
       if (flag) k_logit_rows<FAMILY, MT, true><<<grid, block, 0, s>>>(x);
@@ -255,21 +286,21 @@ hipError_t launch_mt(const LogitArgs& x, int what, bool flag, hipStream_t s) {
 // 16-dim output tiles per chain: 1, 2, 4 or 8 (D <= HMC_LOGIT_MAX_D = 128).  An instance runs all
 // its k-steps and output tiles whatever D is (see logit_grad).
 template <int FAMILY>
-hipError_t launch_family(LogitArgs x, int what, bool flag, hipStream_t s) {
+hipError_t launch_family(LogitArgs x, int what, bool flag, const hmc_adapt* ad, hipStream_t s) {
   if (x.a.n == 0) return hipSuccess;
   x.a.ntiles = (x.a.n + 15) / 16;
   const int mt = (x.a.D + 15) / 16;
-  if (mt <= 1) return launch_mt<FAMILY, 1>(x, what, flag, s);
-  if (mt <= 2) return launch_mt<FAMILY, 2>(x, what, flag, s);
-  if (mt <= 4) return launch_mt<FAMILY, 4>(x, what, flag, s);
-  if (mt <= 8) return launch_mt<FAMILY, 8>(x, what, flag, s);
+  if (mt <= 1) return launch_mt<FAMILY, 1>(x, what, flag, ad, s);
+  if (mt <= 2) return launch_mt<FAMILY, 2>(x, what, flag, ad, s);
+  if (mt <= 4) return launch_mt<FAMILY, 4>(x, what, flag, ad, s);
+  if (mt <= 8) return launch_mt<FAMILY, 8>(x, what, flag, ad, s);
   return hipErrorInvalidValue;
 }
 
-hipError_t launch(const LogitArgs& x, int family, int what, bool flag, hipStream_t s) {
+hipError_t launch(const LogitArgs& x, int family, int what, bool flag, hipStream_t s, const hmc_adapt* ad = nullptr) {
   switch (family) {
-    case HMC_GLM_BERNOULLI: return launch_family<HMC_GLM_BERNOULLI>(x, what, flag, s);
-    case HMC_GLM_POISSON: return launch_family<HMC_GLM_POISSON>(x, what, flag, s);
+    case HMC_GLM_BERNOULLI: return launch_family<HMC_GLM_BERNOULLI>(x, what, flag, ad, s);
+    case HMC_GLM_POISSON: return launch_family<HMC_GLM_POISSON>(x, what, flag, ad, s);
   }
   return hipErrorInvalidValue;
 }
@@ -279,8 +310,20 @@ hipError_t launch(const LogitArgs& x, int family, int what, bool flag, hipStream
 hipError_t launch_logit_init(const LogitArgs& x, int family, bool replay, hipStream_t s) {
   return launch(x, family, 0, replay, s);
 }
-hipError_t launch_logit_iters(const LogitArgs& x, int family, bool replay, hipStream_t s) {
-  return launch(x, family, 1, replay, s);
+hipError_t launch_logit_iters(const LogitArgs& x, int family, bool replay, hipStream_t s, const hmc_adapt* ad) {
+  return launch(x, family, 1, replay, s, ad);
+}
+
+// hmc_adapt_init: the initial adaptation state of n chains (hmc_adapt.hpp), s0 NULL: s = 1
+__global__ void k_adapt_init(double* state, int64_t n, const double* s0) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) adapt_store(state + i * HMC_ADAPT_STRIDE, adapt_initial(s0 ? s0[i] : 1.0));
+}
+
+hipError_t launch_adapt_init(double* state, int64_t n, const double* s0, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  k_adapt_init<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s>>>(state, n, s0);
+  return hipGetLastError();
 }
 hipError_t launch_logit_rows(const LogitArgs& x, int family, bool leapfrog, hipStream_t s) {
   return launch(x, family, 2, leapfrog, s);

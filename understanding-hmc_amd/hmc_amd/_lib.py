@@ -72,6 +72,17 @@ class GLM(ctypes.Structure):
                 ("prior_prec", c_dp), ("family", ctypes.c_int32)]
 
 
+ADAPT_STRIDE = 8   # include/hmc.h HMC_ADAPT_STRIDE: doubles of adaptation state per chain
+(ADAPT_LOG_S, ADAPT_LOG_S_BAR, ADAPT_H_BAR, ADAPT_M, ADAPT_MU, ADAPT_SUM_ADAPT, ADAPT_SUM_AFTER,
+ ADAPT_N_AFTER) = range(8)
+
+
+class Adapt(ctypes.Structure):
+    """hmc_adapt: the per-chain step-size adaptation state (device pointer) and its parameters."""
+    _fields_ = [("state", c_dp), ("adapt_end", ctypes.c_int32), ("delta", ctypes.c_double),
+                ("gamma", ctypes.c_double), ("t0", ctypes.c_double), ("kappa", ctypes.c_double)]
+
+
 # Exported symbols (tests check every one of these is present; keep in sync with include/hmc.h)
 SYMBOLS = {
     "hmc_version": (ctypes.c_char_p, []),
@@ -139,6 +150,14 @@ SYMBOLS = {
     "hmc_glm_nuts_workspace_size": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int32]),
     "hmc_glm_nuts_iters": (ctypes.c_int, [ctypes.POINTER(GLM), ctypes.POINTER(Kinetic), ctypes.POINTER(Schedule),
                                           ctypes.POINTER(Replay), ctypes.POINTER(State), c_dp, ctypes.c_int64, c_dp]),
+    "hmc_adapt_init": (ctypes.c_int, [c_dp, ctypes.c_int64, c_dp, c_dp]),
+    "hmc_glm_random_iters_adapt": (ctypes.c_int, [ctypes.POINTER(GLM), ctypes.POINTER(Kinetic),
+                                                  ctypes.POINTER(Schedule), ctypes.POINTER(Replay),
+                                                  ctypes.POINTER(State), ctypes.POINTER(Adapt), c_dp]),
+    "hmc_glm_nuts_iters_adapt": (ctypes.c_int, [ctypes.POINTER(GLM), ctypes.POINTER(Kinetic),
+                                                ctypes.POINTER(Schedule), ctypes.POINTER(Replay),
+                                                ctypes.POINTER(State), c_dp, ctypes.c_int64,
+                                                ctypes.POINTER(Adapt), c_dp]),
     "hmc_rng_normals": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                        ctypes.c_int32, c_dp, c_dp]),
     "hmc_philox": (ctypes.c_int, [ctypes.c_uint32] * 6 + [ctypes.c_int64, c_dp, c_dp]),

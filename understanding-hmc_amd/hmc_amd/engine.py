@@ -260,6 +260,8 @@ class RandomEngine:
             arr["E_chain"], arr["dE_chain"] = self.E_chain, self.dE_chain
         if getattr(self, "ws", None) is not None:
             arr["ws"] = self.ws
+        if getattr(self, "adapt_state", None) is not None:
+            arr["adapt_state"] = self.adapt_state           # GLM engines: step-size adaptation state
         if self._order is not None:
             arr["order_ws"] = self._order                   # dense: tile order + gradient cache of q
         if diag is not None:
@@ -289,7 +291,8 @@ class RandomEngine:
                 raise AssertionError(f"checkpoint does not match this engine: {bad}")
             for k, t in (("q", self.q), ("E_prev", self.E_prev), ("counters", self.counters),
                          ("q_chain", self.q_chain), ("E_chain", self.E_chain), ("dE_chain", self.dE_chain),
-                         ("ws", getattr(self, "ws", None)), ("order_ws", self._order)):
+                         ("ws", getattr(self, "ws", None)), ("adapt_state", getattr(self, "adapt_state", None)),
+                         ("order_ws", self._order)):
                 if t is not None and k in z.files:
                     t.copy_(torch.as_tensor(z[k]).to(self.device))
             if self._order is not None and "order_ws" not in z.files:
@@ -440,6 +443,63 @@ class GLMEngine(_KernelTargetEngine):
 
     _init_entry, _run_entry, _what = "hmc_glm_chain_init", "hmc_glm_random_iters", "GLM"
 
+    def __init__(self, *args, adapt_step=False, adapt_delta=0.8, step_scale0=None, **kw):
+        """adapt_step: every chain adapts a multiplier of `dt` during warm-up (iterations
+        1 <= i < warm_up) by dual averaging towards a mean acceptance statistic adapt_delta, and runs
+        at the averaged multiplier afterwards.  step_scale0: the multipliers to start from, a scalar
+        or (N,) (default 1); without adapt_step they stay as given.  Either makes run() call the
+        hmc_*_adapt entry with the (N, 8) state `adapt_state` (include/hmc.h: hmc_adapt), which
+        save() / restore() carry."""
+        super().__init__(*args, **kw)
+        self._setup_adapt(adapt_step, adapt_delta, step_scale0)
+
+    def _setup_adapt(self, adapt_step, adapt_delta, step_scale0):
+        self.adapt_step, self.adapt_delta = bool(adapt_step), float(adapt_delta)
+        self.adapt_state = self._adapt = self._s0 = None
+        if not (adapt_step or step_scale0 is not None):
+            return
+        if not 0.0 < self.adapt_delta < 1.0:
+            raise AssertionError("adapt_delta=%r: the target acceptance statistic lies in (0, 1)" % (adapt_delta,))
+        if step_scale0 is not None:
+            s0 = np.broadcast_to(np.asarray(step_scale0, dtype=np.float64), (self.N,))
+            if not np.all(np.isfinite(s0) & (s0 > 0)):
+                raise AssertionError("step_scale0 must be positive and finite")
+            self._s0 = _dev(s0, self.device)
+        if self.N == 0:
+            return
+        self.adapt_state = torch.zeros((self.N, H.ADAPT_STRIDE), dtype=torch.float64, device=self.device)
+        H.check(H.lib().hmc_adapt_init(H.ptr(self.adapt_state), self.N, H.ptr(self._s0), self.stream()),
+                "hmc_adapt_init")
+        # Hoffman & Gelman's gamma, t0, kappa; adapt_end = warm_up: the reference's warm-up iterations
+        self._adapt = H.Adapt(H.ptr(self.adapt_state), self.warm_up if self.adapt_step else 0, self.adapt_delta,
+                              0.05, 10.0, 0.75)
+
+    @property
+    def step_scale(self):
+        """(N,) device tensor of the adapted multipliers exp(log_s_bar); None without adaptation."""
+        return None if self.adapt_state is None else torch.exp(self.adapt_state[:, H.ADAPT_LOG_S_BAR])
+
+    def _meta(self):
+        meta = super()._meta()
+        if self.adapt_state is not None:       # a checkpoint of an adaptive run resumes only into one
+            meta.update(adapt_step=self.adapt_step, adapt_delta=self.adapt_delta)
+        return meta
+
+    def restore(self, path, diag=None):
+        with np.load(path, allow_pickle=False) as z:
+            saved = "adapt_state" in z.files
+        if saved != (self.adapt_state is not None):
+            raise AssertionError("checkpoint %s a step-size adaptation state, this engine %s"
+                                 % (("has", "runs without one") if saved else ("has no", "needs one")))
+        return super().restore(path, diag)
+
+    def run(self, it0, it1):
+        """Iterations [it0, it1) of every chain in ONE fused kernel launch."""
+        if self._adapt is None:
+            return super().run(it0, it1)
+        H.check(H.lib().hmc_glm_random_iters_adapt(self.T, self.K, self.schedule(it0, it1), self._replay, self.S,
+                                                   self._adapt, self.stream()), "hmc_glm_random_iters_adapt")
+
     @classmethod
     def check_supported(cls, target, cov_p):
         """NotImplementedError, before anything touches the device, for what the kernels do not take."""
@@ -470,10 +530,11 @@ class GLMNutsEngine(GLMEngine):
 
     def __init__(self, target, n_chains, n_iter, warm_up, thin, d_max, dt, cov_p=None, rng="philox", seed=0,
                  fp_mode="fast", chain_offset=0, store_chain=True, store_energy=True, on_dmax="raise",
-                 device=None, iters_per_call=None):
+                 device=None, iters_per_call=None, adapt_step=False, adapt_delta=0.8, step_scale0=None):
         super().__init__(target, n_chains, n_iter, warm_up, thin, 5, 20, dt, cov_p=cov_p, rng=rng, seed=seed,
                          fp_mode=fp_mode, chain_offset=chain_offset, store_chain=store_chain,
-                         store_energy=store_energy, n_save=0, device=device)
+                         store_energy=store_energy, n_save=0, device=device, adapt_step=adapt_step,
+                         adapt_delta=adapt_delta, step_scale0=step_scale0)
         assert on_dmax in ("raise", "break")
         self.d_max = int(d_max)
         self.on_dmax = 0 if on_dmax == "raise" else 1
@@ -492,6 +553,11 @@ class GLMNutsEngine(GLMEngine):
 
     def run(self, it0, it1):
         """Iterations [it0, it1) of every chain in one launch."""
+        if self._adapt is not None:
+            H.check(H.lib().hmc_glm_nuts_iters_adapt(self.T, self.K, self.schedule(it0, it1), self._replay, self.S,
+                                                     H.ptr(self.ws), self.ws.numel() * 8, self._adapt,
+                                                     self.stream()), "hmc_glm_nuts_iters_adapt")
+            return
         H.check(H.lib().hmc_glm_nuts_iters(self.T, self.K, self.schedule(it0, it1), self._replay, self.S,
                                            H.ptr(self.ws), self.ws.numel() * 8, self.stream()), "hmc_glm_nuts_iters")
 

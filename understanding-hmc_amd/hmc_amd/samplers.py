@@ -126,13 +126,28 @@ class HMC_sampler(sampler):
                     between diagnostics updates
       iters_per_launch : iterations fused in one kernel launch (default: all)
       chain_offset : global id of this object's first chain (multi-GPU sharding)
+      adapt_step : GLMTarget only (anything else raises NotImplementedError here, before any launch).
+                 Every chain adapts a multiplier s of `dt` (effective step s * dt, scalar or vector;
+                 cov_p unchanged) during the reference's warm-up iterations 1 <= i < warm_up_num, by
+                 the dual averaging of Hoffman & Gelman 2014 towards a mean acceptance statistic
+                 `adapt_delta`, and runs at the averaged multiplier from warm_up_num on.  Per chain:
+                 results still depend on nothing but the global chain id.  mu = log(step_scale0), so
+                 `dt` is the point the iterates shrink to (Stan's log(10 s0) overflows exp(z) of the
+                 Poisson family on its first jump).  After a run: `step_scale` (Nchain,)
+                 the final multipliers exp(log_s_bar); `accept_stat_warm_up`, `accept_stat` the mean
+                 acceptance statistic over chains and iterations before / from warm_up_num (Random:
+                 min(1, exp(-dE)); NUTS: the mean over the tree's points of min(1, exp(E_init - E)));
+                 `adapt_state` the (Nchain, 8) state array.  accept_R keeps the reference's meaning
+      adapt_delta : target of the mean acceptance statistic, in (0, 1) (default 0.8)
+      step_scale0 : multipliers to start from, a scalar or (Nchain,) (default 1), e.g. a pooled
+                 `step_scale` of an earlier run; without adapt_step they stay as given
     """
 
     def __init__(self, D, V, dVdq, Nchain=2, Niter=1000, thin_rate=1, warm_up_num=0,
                  cov_p=None, sampler_type="Fixed", L=None, global_dt=True, dt=None,
                  L_low=None, L_high=None, log2L=None, d_max=10, target=None, rng="replay", seed=0,
                  fp_mode="exact", device=None, store_chain=True, iters_per_launch=None, chain_offset=0,
-                 stream_tmax=64, stream_feed=60):
+                 stream_tmax=64, stream_feed=60, adapt_step=False, adapt_delta=0.8, step_scale0=None):
         sampler.__init__(self, D=D, target_lnL=None, Nchain=Nchain, Niter=Niter, thin_rate=thin_rate,
                          warm_up_num=warm_up_num)
         self.V = V
@@ -189,6 +204,17 @@ class HMC_sampler(sampler):
             if self.sampler_type == "NUTS" and self._kernel_target[5] is None:
                 raise NotImplementedError("NUTS on a %s target is not supported (sampler_type='Random')" % name)
             engine.check_supported(target, self.cov_p)
+        # step-size adaptation: the GLM kernels alone have the ADAPT forms
+        self._adapt_kw = {}
+        if adapt_step or step_scale0 is not None:
+            if not isinstance(target, GLMTarget):
+                raise NotImplementedError("adapt_step / step_scale0 are supported for a GLMTarget only "
+                                          "(sampler_type 'Random' or 'NUTS')")
+            if not 0.0 < float(adapt_delta) < 1.0:
+                raise AssertionError("adapt_delta=%r: the target acceptance statistic lies in (0, 1)" % (adapt_delta,))
+            self._adapt_kw = dict(adapt_step=bool(adapt_step), adapt_delta=float(adapt_delta),
+                                  step_scale0=step_scale0)
+        self.step_scale = self.accept_stat_warm_up = self.accept_stat = self.adapt_state = None
         self.n_leapfrog = 0
         self.q_chain_device = None
 
@@ -301,7 +327,7 @@ class HMC_sampler(sampler):
         eng = engine(self.target(), self.Nchain, self.Niter, self.warm_up_num, self.thin_rate, self.L_low,
                      self.L_high, self.dt, cov_p=self.cov_p, rng=self.rng, seed=self.seed,
                      fp_mode=self.fp_mode, chain_offset=self.chain_offset, store_chain=self.store_chain,
-                     n_save=n_save, device=self.device)
+                     n_save=n_save, device=self.device, **self._adapt_kw)
         if self.rng == "replay":
             eng.set_replay(*(getattr(self, "_random_replay", None) or self._replay_streams_random()))
         t0 = time.time()
@@ -381,6 +407,7 @@ class HMC_sampler(sampler):
             self.q_chain = None                     # streaming mode: statistics only
         self.E_chain = eng.E_chain.cpu().numpy()[:, :, None]
         self.dE_chain = eng.dE_chain.cpu().numpy()[:, :, None]
+        self._read_adapt(eng)
         if eng.n_save:
             n_save = eng.n_save
             self.decision_chain = np.zeros((n_save + 1, 1), dtype=int)
@@ -388,6 +415,19 @@ class HMC_sampler(sampler):
             T_ = eng.traj.cpu().numpy()
             tl = eng.traj_len.cpu().numpy()
             self.phi_q = [T_[i, :tl[i]].copy() for i in range(n_save) if tl[i] > 0]
+
+    def _read_adapt(self, eng):
+        """step_scale, accept_stat_warm_up, accept_stat and adapt_state of a run through the _adapt
+        entries (include/hmc.h: hmc_adapt state slots); None otherwise."""
+        st = getattr(eng, "adapt_state", None)
+        if st is None:
+            return
+        st = st.cpu().numpy()
+        self.adapt_state = st
+        self.step_scale = np.exp(st[:, H.ADAPT_LOG_S_BAR])
+        n_adapt, n_after = st[:, H.ADAPT_M].sum(), st[:, H.ADAPT_N_AFTER].sum()
+        self.accept_stat_warm_up = st[:, H.ADAPT_SUM_ADAPT].sum() / n_adapt if n_adapt > 0 else None
+        self.accept_stat = st[:, H.ADAPT_SUM_AFTER].sum() / n_after if n_after > 0 else None
 
     def set_nuts_replay(self, p0, P, tape):
         """Explicit NUTS draw streams (rng="replay"): p0 (Nchain, D), p (Nchain, Niter, D) and a
@@ -423,7 +463,8 @@ class HMC_sampler(sampler):
                      chain_offset=self.chain_offset, store_chain=self.store_chain, on_dmax=on_dmax,
                      device=self.device,
                      iters_per_call=(self.iters_per_launch or self.Niter) if self.store_chain
-                     else (self.iters_per_launch or 20))                      # (_run's launch sizes)
+                     else (self.iters_per_launch or 20),                      # (_run's launch sizes)
+                     **self._adapt_kw)
         if rng == "replay":
             eng.set_replay(*tape)
         t0 = time.time()
@@ -452,6 +493,7 @@ class HMC_sampler(sampler):
         self.q_chain = eng.q_chain.cpu().numpy() if eng.q_chain is not None else None
         self.E_chain = eng.E_chain.cpu().numpy()[:, :, None]
         self.dE_chain = eng.dE_chain.cpu().numpy()[:, :, None]
+        self._read_adapt(eng)
         print("Compute acceptance rate: By default equal to 1.")                 # :800-805
         if self.warm_up_num > 0:
             self.accept_R_warm_up = 1.
