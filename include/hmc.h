@@ -202,7 +202,12 @@ int32_t hmc_random_leapfrog_form(const hmc_target* t, const hmc_kinetic* k, cons
 /* Which layout hmc_random_iters picks for a diagonal target (host only, no device access):
  * out[0] = K coordinate pairs per lane, out[1] = lanes per chain, out[2] = chains per wave,
  * out[3] = 1 for the wave-per-chain kernels (hmc_wave.hip), 0 for the lane-group kernel.
- * Only t->D, t->kind, s->L_low and s->L_high are read.  The lane-group kernel (D <= 64) takes 36
+ * Only t->D, t->kind, t->q0, t->prec, s->L_low, s->L_high, s->fp_mode and s->rng_mode are read.
+ * 97 <= D <= 112 on an identity target in FAST mode with Philox draws answers (4, 16, 4, 0): the
+ * four-chains-per-wave kernel (hmc_rows.hip: 16 lanes per chain with 7 coordinates each, reported
+ * as 4 pairs), which takes the launches with an identity mass, a scalar dt in the three-term range
+ * and no chain-0 capture; the others run the wave-per-chain kernel.
+ * The lane-group kernel (D <= 64) takes 36
  * layouts over all trajectory-length ranges: K = 1 on 1..32 lanes, K = 2 on 3, 7, 9, 11 or 12
  * lanes, K = 5 on 1..5 lanes, K = 4 on 3 or 7 lanes and K = 8 on 3 lanes; the many-pairs-per-lane
  * ones (K = 4, K = 8, K = 5 on 3..5 lanes) only when the trajectory length is constant

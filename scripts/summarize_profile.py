@@ -16,7 +16,7 @@ out, tag = sys.argv[1], sys.argv[2]
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 prof = os.path.join(ROOT, "profiles")
 os.makedirs(prof, exist_ok=True)
-HOT = ("k_wave_iters", "k_random_iters", "k_dense_iters", "k_nuts_iters")
+HOT = ("k_wave_iters", "k_rows_iters", "k_random_iters", "k_dense_iters", "k_nuts_iters")
 
 
 def one(pattern):

@@ -359,6 +359,17 @@ hmc_status hmc_random_layout(const hmc_target* t, const hmc_schedule* s, int32_t
   if (hmc::big_path(false, t->D)) return fail(HMC_ENOTSUP, "hmc_random_layout: D=%d runs the large-D path", t->D);
   const hmc::Layout lay = hmc::choose_layout(t->D, s->L_low, s->L_high);
   if (lay.K == 0) return fail(HMC_ENOTSUP, "D=%d too large for the diagonal kernels", t->D);
+  // 97 <= D <= 112, FAST, Philox, identity target: the four-chains-per-wave kernel (hmc_rows.hip)
+  // takes the production launches (identity mass, scalar dt in the three-term range, no capture):
+  // 16 lanes per chain with 7 coordinates each, reported as ceil(7 / 2) pairs per lane
+  if (hmc::rows_shape(t->D, s->L_low, s->L_high) && s->fp_mode != HMC_MODE_EXACT && s->rng_mode != HMC_RNG_REPLAY &&
+      !t->q0 && !t->prec) {
+    out[0] = 4;
+    out[1] = 16;
+    out[2] = 4;
+    out[3] = 0;
+    return HMC_OK;
+  }
   out[0] = lay.K;
   out[1] = lay.lpc;
   out[2] = lay.cpw;

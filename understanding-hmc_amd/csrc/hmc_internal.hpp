@@ -103,6 +103,11 @@ hipError_t launch_wave_iters(const RandArgs& a, int K, bool exact, bool gen, boo
 // wave-per-chain layout, FAST mode, identity target and mass with a scalar dt inside the range
 // where recovering the momentum from the last two points is safe.
 bool leapfrog_three_term(const RandArgs& a, const Layout& lay, bool exact, bool gen);
+// Four chains per wavefront for 97 <= D <= 112 (hmc_rows.hip): rows_shape is the part of the choice
+// that the dimension and the trajectory lengths decide, rows_kernel the whole of it for one launch.
+bool rows_shape(int D, int L_low, int L_high);
+bool rows_kernel(const RandArgs& a, const Layout& lay, bool exact, bool gen, bool replay);
+hipError_t launch_rows_iters(const RandArgs& a, hipStream_t s);
 hipError_t launch_dense_init(const DenseArgs& a, bool replay, hipStream_t s);
 hipError_t launch_dense_iters(const DenseArgs& a, bool exact, bool replay, hipStream_t s);
 int64_t dense_order_ints(int64_t n);   // int32 scratch of the L-ordering (order[n] + histograms)

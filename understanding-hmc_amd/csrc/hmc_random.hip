@@ -474,8 +474,29 @@ bool leapfrog_three_term(const RandArgs& a, const Layout& lay, bool exact, bool 
 #endif
 }
 
+// Four chains per wavefront, one 16-lane row each (hmc_rows.hip): the shapes it is built for.  The
+// kernel packs L in 24 bits for its tallies and takes no empty trajectory.
+// -DHMC_NO_ROWS builds the library that never picks it (A/B).
+bool rows_shape(int D, int L_low, int L_high) {
+#ifdef HMC_NO_ROWS
+  return false;
+#else
+  return D >= 97 && D <= 112 && L_low >= 1 && L_high <= (1 << 12);
+#endif
+}
+
+// ... and the launches it takes: those of the production wave instance (FAST, identity target and
+// mass, three-term leapfrog, Philox, no chain-0 capture or debug hooks), with a sample window whose
+// rows of the wave's four chains lie within a 32-bit byte offset of the first.
+bool rows_kernel(const RandArgs& a, const Layout& lay, bool exact, bool gen, bool replay) {
+  const bool full = a.traj_q != nullptr || a.dbg != 0 || a.dbgL >= 0;
+  if (replay || full || !rows_shape(a.D, a.L_low, a.L_high) || !leapfrog_three_term(a, lay, exact, gen)) return false;
+  return !a.qc || 4 * (int64_t)a.Lq * a.D * 8 < (int64_t)1 << 31;
+}
+
 hipError_t launch_random_iters(const RandArgs& a, const Layout& lay, bool exact, bool gen, bool replay,
                                hipStream_t s) {
+  if (rows_kernel(a, lay, exact, gen, replay)) return launch_rows_iters(a, s);
   if (wave_layout(lay))
     return launch_wave_iters(a, lay.K, exact, gen, replay, leapfrog_three_term(a, lay, exact, gen), s);
   const dim3 grid = grid_for(a);

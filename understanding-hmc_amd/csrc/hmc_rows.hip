@@ -1,0 +1,370 @@
+// hmc_rows.hip — four chains per wavefront for the FAST identity-target Random kernel, D = 97..112.
+//
+// Same semantics and the same per-coordinate arithmetic as the production wave-per-chain instance
+// (hmc_wave.hip: FAST, identity precision and mass, Philox, three-term leapfrog, no capture), in
+// another layout: chain 4 * wave + r lives in the 16-lane DPP row r, and lane s of the row holds
+// coordinates s + 16 j, j < 7 (slots past D hold exact zeros).  What the wave kernel pays once per
+// wave (the energy reduction, the accept test, parking, tallies, addresses) is paid once per four
+// chains here.  Every q is bit-identical to the wave kernel's; the energies are row sums
+// (row_shr 1/2/4/8) instead of the full-wave sum, so E and dE move in the last bits.
+//   * trajectory lengths differ per row: the paired-step loop runs to the wave's longest
+//     trajectory and rows that are done are switched off through EXEC;
+//   * the decision is formed in lane 15 of each row, the four bits are widened to row masks on the
+//     SALU, and a reject restores under that EXEC mask;
+//   * momentum: every pass draws 16 consecutive pairs of each row's own (pair, iteration) stream
+//     into that chain's LDS ring (stream order, ten 128-B chunks; the first is mirrored behind the
+//     tenth, so that a read which starts in the last chunk runs on without a per-lane wrap).
+// Odd D needs no instance of its own: coordinates are read from the ring one by one, so the pair
+// that holds the dimension past D is only ever read by a masked slot.
+// Dynamic LDS: the Box–Muller tables (32 KB) + 8 waves x 4 chains x 1408 B = 76 KB per block: two
+// blocks per CU, four waves per SIMD (112 VGPRs, no scratch).  Two blocks rather than one of 16 waves:
+// a block's start-up (tables, state loads, first ring fill) and its tail then overlap the other's
+// iterations (measured 5% faster).
+#include "hmc_device.hpp"
+#include "hmc_internal.hpp"
+#include "hmc_target_ops.hpp"
+
+namespace hmc {
+
+namespace {
+
+constexpr int kRowLanes = 16;                      // one DPP row per chain
+constexpr int kRowChains = kWave / kRowLanes;      // chains per wave
+constexpr int kRowsBlock = 512;                    // 8 waves
+constexpr int kRowChunkBytes = 8 * kRowLanes;      // one slot of a row: 16 doubles
+constexpr uint32_t kRowRingBytes = 10 * kRowChunkBytes;   // per chain: at most (112 - 1) + 32 doubles wait in it
+constexpr uint32_t kRowRingAlloc = 11 * kRowChunkBytes;   // + the mirror of chunk 0 (reads end 248 B past a chunk's start)
+constexpr size_t kRowsLds =
+    8 * (size_t)kNormalTableDoubles + (size_t)(kRowsBlock / kWave) * kRowChains * kRowRingAlloc;
+
+// x.x of the lane's coordinates, the chain hmc_wave.hip's wave_sumsq_fma forms
+template <int C>
+__device__ __forceinline__ double rows_sumsq(const double (&v)[C], double s0) {
+  double s = __builtin_fma(v[1], v[1], s0);
+  s = __builtin_fma(v[0], v[0], s);
+#pragma unroll
+  for (int e = 2; e < C; ++e) s = __builtin_fma(v[e], v[e], s);
+  return s;
+}
+
+// sums over each 16-lane row: lane 15 of the row holds the total (EXEC all ones)
+__device__ __forceinline__ double row_sum_l15(double v) {
+  v += dpp_u<0x111>(v);        // row_shr:1 (bound_ctrl: lanes shifted in from outside the row read 0)
+  v += dpp_u<0x112>(v);        // row_shr:2
+  v += dpp_u<0x114>(v);        // row_shr:4
+  v += dpp_u<0x118>(v);        // row_shr:8
+  return v;
+}
+
+// max of two wave-uniform values on the SALU (written in C the compiler takes it to the VALU)
+__device__ __forceinline__ int s_max_i32(int a, int b) {
+  int r;
+  asm("s_max_i32 %0, %1, %2" : "=s"(r) : "s"(a), "s"(b) : "scc");
+  return r;
+}
+
+// n += 1 in the lanes of `mask` (one VALU: the mask is the carry-in)
+__device__ __forceinline__ void add_mask(uint32_t& n, uint64_t mask) {
+  uint64_t co;
+  asm("v_addc_co_u32_e64 %0, %1, %0, 0, %2" : "+v"(n), "=&s"(co) : "s"(mask));
+}
+
+// Parks v (valid in lane 15 of each row) by shifting each row of buf one lane down and taking v in
+// lane 15 (row_shl:1, the lane without a source keeps `old`): after n parks the values sit in lanes
+// 16 - n .. 15, oldest first.  No LDS round trip.
+__device__ __forceinline__ double park_row_shift(double buf, double v) {
+  const int lo = __builtin_amdgcn_update_dpp(__double2loint(v), __double2loint(buf), 0x101, 0xF, 0xF, false);
+  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(v), __double2hiint(buf), 0x101, 0xF, 0xF, false);
+  return __hiloint2double(hi, lo);
+}
+
+template <int C>
+__global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_rows_iters(RandArgs a) {
+  static_assert(C == 7, "seven coordinates per lane: D in (96, 112], only the last slot is partial");
+  extern __shared__ __attribute__((aligned(16))) double s_rows[];
+  double* const s_ntab = s_rows;                                     // Box–Muller tables
+  char* const ring_b = reinterpret_cast<char*>(s_rows + kNormalTableDoubles);
+  init_normal_tables(s_ntab);
+  __syncthreads();
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wib = threadIdx.x / kWave;
+  const int64_t c0 = (int64_t)kRowChains * uniform_i(blockIdx.x * (kRowsBlock / kWave) + wib);
+  if (c0 >= a.n) return;                                  // whole wave, uniform
+  const int r = lane / kRowLanes, s = lane & (kRowLanes - 1);
+  const int64_t c = c0 + r;
+  const bool valid = c < a.n;                             // rows past the last chain run along; masked at loads, stores, tallies
+  const bool v6 = s + kRowLanes * (C - 1) < a.D;          // the last slot exists for this lane
+  const bool st6 = valid && v6;
+  const uint64_t gc = (uint64_t)(a.chain_offset + c);
+  const uint32_t ringrow = (uint32_t)(wib * kRowChains + r) * kRowRingAlloc;   // this chain's ring (bytes)
+
+  // Generator: lane s of a row draws pair gk of iteration git of its chain; a pass moves it 16 pairs
+  // on (npairs >= 49: one wrap at most).  gen_n: pairs drawn per chain, gposb: their ring position.
+  int gen_n = 0;
+  uint32_t gposb = 0;
+  uint32_t gk = s, git = a.it0;
+  const uint32_t wlane = ringrow + 16 * s;
+  int rbaseb = 0;                                         // ring position (bytes) of the next iteration's doubles
+  const int dpb = 16 * a.npairs;                          // stream bytes per iteration
+  const uint32_t rlane = ringrow + 8 * s;
+  double q[C], p[C], qi[C];
+  // 16 pairs on: gk += 16, and past the iteration's last pair gk -= npairs, git += 1 (four VALU: the
+  // borrow of gk - npairs picks both)
+  auto advance = [&](uint32_t& k, uint32_t& i) {
+    uint64_t bo;
+    uint32_t tk;
+    asm("v_add_u32_e32 %0, 16, %0\n\t"
+        "v_subrev_co_u32_e32 %2, vcc, %4, %0\n\t"
+        "v_subb_co_u32_e64 %1, %3, %1, -1, vcc\n\t"
+        "v_cndmask_b32_e32 %0, %2, %0, vcc"
+        : "+v"(k), "+v"(i), "=&v"(tk), "=&s"(bo)
+        : "s"(a.npairs)
+        : "vcc");
+  };
+  auto ring_momentum = [&](int it) {
+    const int need = (it - a.it0 + 1) * a.npairs;
+    while (gen_n < need) {                                // wave-uniform
+      double z0, z1;
+      normal_pair_tab(draw_block(gk, git, gc, a.k0, a.k1), s_ntab, z0, z1);
+      // a pass fills two whole chunks (1280 = 5 * 256: it never straddles the wrap)
+      char* const w = ring_b + (gposb + wlane);
+      *reinterpret_cast<double2*>(w) = make_double2(z0, z1);
+      // the mirror of chunk 0: the pass's first eight pairs
+      if (gposb == 0 && s < kRowLanes / 2) *reinterpret_cast<double2*>(w + kRowRingBytes) = make_double2(z0, z1);
+      gen_n += kRowLanes;
+      gposb += 16 * kRowLanes;
+      if (gposb >= kRowRingBytes) gposb -= kRowRingBytes;
+      advance(gk, git);
+    }
+    __builtin_amdgcn_wave_barrier();
+    // slot j starts in chunk (cb + j) mod 10 (SALU) and this lane reads ob + 8 s bytes on, possibly
+    // in the next chunk (the mirror after the tenth)
+    const uint32_t cbb = (uint32_t)rbaseb & ~(uint32_t)(kRowChunkBytes - 1);
+    const uint32_t a0 = ((uint32_t)rbaseb - cbb) + rlane;   // < 128 + 120
+#pragma unroll
+    for (int j = 0; j < C; ++j) {
+      uint32_t cj = cbb + kRowChunkBytes * j;
+      if (cj >= kRowRingBytes) cj -= kRowRingBytes;
+      p[j] = *reinterpret_cast<const double*>(ring_b + (opaque_s32(cj) + a0));
+    }
+    p[C - 1] = v6 ? p[C - 1] : 0.0;                       // dimension past D: no such coordinate
+    rbaseb += dpb;
+    if (rbaseb >= (int)kRowRingBytes) rbaseb -= kRowRingBytes;
+  };
+
+  double* const qst = a.q + c * (int64_t)a.D + s;
+#pragma unroll
+  for (int j = 0; j < C; ++j) {
+    q[j] = 0.0;
+    if (j < C - 1 ? valid : st6) q[j] = qst[kRowLanes * j];
+  }
+  double Eprev = valid ? a.Eprev[c] : 0.0;
+  __builtin_amdgcn_s_waitcnt(0x0F70);                    // retire state loads before the loop (vmcnt(0))
+
+  ring_momentum(a.it0);
+  const double hlogc = 0.5 * a.logc;
+  double m0l = rows_sumsq<C>(q, 0.0);                    // this lane's part of q.q
+  double e0l = rows_sumsq<C>(p, m0l);                    // ... and of q.q + p.p at the iteration start
+  double E0 = 0.0;
+
+  int row = 0, phase = 0;
+  if (a.it0 >= a.wu) {
+    row = (a.it0 - a.wu) / a.thin;
+    phase = (a.it0 - a.wu) - row * a.thin;
+  }
+  int qslot = row % a.Lq;
+  double Ebuf = 0.0, dEbuf = 0.0;
+  int row_first = 0, nbuf = 0;
+  const uint32_t bprow = (uint32_t)(lane & ~(kRowLanes - 1)) * 4;
+  double* const Ec = a.Ec ? a.Ec + c * (int64_t)a.Lc + s : nullptr;
+  double* const dEc = a.dEc ? a.dEc + c * (int64_t)a.Lc + s : nullptr;
+  // sample rows: wave-uniform base (chain c0, row qslot) + this lane's 32-bit byte offset
+  char* const qcb = a.qc ? reinterpret_cast<char*>(a.qc + c0 * (int64_t)a.Lq * a.D) : nullptr;
+  const uint32_t qoff = (uint32_t)(r * a.Lq * a.D + s) * 8u;   // host: 3 Lq D 8 + 1 KB < 2^31
+  auto flush_E = [&](int n) {          // rows row_first .. row_first + n - 1 from lanes 0 .. n-1 of each row
+    const int first = kRowLanes - n;   // the n parked values sit in lanes 16 - n .. 15, oldest first
+    if (valid && s >= first) {
+      if (Ec) __builtin_nontemporal_store(Ebuf, Ec + (row_first - first));
+      if (dEc) __builtin_nontemporal_store(dEbuf, dEc + (row_first - first));
+    }
+  };
+  uint32_t n_acc = 0, n_acc_wu = 0, n_lf = 0, n_lf2 = 0, n_oob = 0;   // per lane, the same in a row's lanes
+  int it_base = a.it0 - kRowLanes, draw_L = 0;
+  double draw_lnu = 0.0;
+
+  // (L, 2 log u) of iteration `it` of the row's chain: lane s drew iteration it_base + s
+  int L_nxt = 0;
+  double lnu_nxt = 0.0;
+  auto fetch_L = [&](int it) {
+    if (it - it_base >= kRowLanes) {
+      it_base = it;
+      const uint4 rr = draw_block(kDrawSlot, (uint32_t)(it + s), gc, a.k0, a.k1);
+      draw_L = uniform_int(rr.x, a.L_low, a.L_high);
+      const double u = u53(rr.z, rr.w);
+      draw_lnu = u > 0.0 ? fast_log(u) : -__builtin_inf();
+      draw_lnu *= 2.0;                                   // compared with 2 dE (exact scaling)
+    }
+    const int bsrc = (int)(bprow + 4u * (uint32_t)(it - it_base));
+    L_nxt = __builtin_amdgcn_ds_bpermute(bsrc, draw_L);
+    lnu_nxt = __hiloint2double(__builtin_amdgcn_ds_bpermute(bsrc, __double2hiint(draw_lnu)),
+                               __builtin_amdgcn_ds_bpermute(bsrc, __double2loint(draw_lnu)));
+  };
+
+  auto iteration = [&](auto post_c, int it) {
+    constexpr bool post = decltype(post_c)::value;
+    const bool write_row = post && ((it == a.niter) || (phase == a.thin - 1));
+    fetch_L(it);
+    const int L = L_nxt;                                  // >= 1 (host)
+    const double lnu = lnu_nxt;
+#pragma unroll
+    for (int e = 0; e < C; ++e) asm("v_mov_b64 %0, %1" : "=v"(qi[e]) : "v"(q[e]));
+    // three-term leapfrog as in hmc_wave.hip; the parity selects are per lane (per row)
+    double (&x)[C] = p;
+    const uint32_t oddm = (uint32_t)__builtin_amdgcn_sbfe(L, 0, 1);   // all ones where L is odd
+    const uint32_t dtlo = __double2loint(a.dt), dthi = __double2hiint(a.dt);
+    const double sh = __hiloint2double(__double2hiint(a.h) ^ ((uint32_t)L << 31), __double2loint(a.h));   // -/+ dt/2
+    const double sq = __hiloint2double(dthi & oddm, dtlo & oddm);       // dt (odd L) or 0
+    const double sx = a.dt - sq;                                        // 0 (odd L) or dt, exact
+#pragma unroll
+    for (int e = 0; e < C; ++e) {
+      double t;
+      asm("v_fma_f64 %0, %1, %2, %3" : "=v"(t) : "v"(sh), "v"(q[e]), "v"(p[e]));
+      x[e] = __builtin_fma(-sx, t, q[e]);                // u[0] (odd L) or u[-1] = u[0] - dt t
+      q[e] = __builtin_fma(sq, t, q[e]);                 // u[1] = u[0] + dt t (odd L) or u[0]
+    }
+    const int np = L >> 1;                                // paired steps of this row
+    const int np_max = s_max_i32(s_max_i32(__builtin_amdgcn_readlane(np, 0), __builtin_amdgcn_readlane(np, 16)),
+                                 s_max_i32(__builtin_amdgcn_readlane(np, 32), __builtin_amdgcn_readlane(np, 48)));
+    // Pairs of steps up to the wave's longest trajectory.  v_cmpx takes the rows that are done out of
+    // EXEC (it only ever shrinks inside the loop: a finished row stays finished), one VALU per pair.
+    if (np_max > 0) {
+      int i;
+      asm volatile("s_mov_b32 %[i], 0\n"
+                   "1:\n\t"
+                   "v_cmpx_lt_i32_e32 vcc, %[i], %[np]\n\t"
+                   "v_fma_f64 %[x0], %[c], %[q0], -%[x0]\n\t"
+                   "v_fma_f64 %[x1], %[c], %[q1], -%[x1]\n\t"
+                   "v_fma_f64 %[x2], %[c], %[q2], -%[x2]\n\t"
+                   "v_fma_f64 %[x3], %[c], %[q3], -%[x3]\n\t"
+                   "v_fma_f64 %[x4], %[c], %[q4], -%[x4]\n\t"
+                   "v_fma_f64 %[x5], %[c], %[q5], -%[x5]\n\t"
+                   "v_fma_f64 %[x6], %[c], %[q6], -%[x6]\n\t"
+                   "v_fma_f64 %[q0], %[c], %[x0], -%[q0]\n\t"
+                   "v_fma_f64 %[q1], %[c], %[x1], -%[q1]\n\t"
+                   "v_fma_f64 %[q2], %[c], %[x2], -%[q2]\n\t"
+                   "v_fma_f64 %[q3], %[c], %[x3], -%[q3]\n\t"
+                   "v_fma_f64 %[q4], %[c], %[x4], -%[q4]\n\t"
+                   "v_fma_f64 %[q5], %[c], %[x5], -%[q5]\n\t"
+                   "v_fma_f64 %[q6], %[c], %[x6], -%[q6]\n\t"
+                   "s_add_i32 %[i], %[i], 1\n\t"
+                   "s_cmp_lt_i32 %[i], %[n]\n\t"
+                   "s_cbranch_scc1 1b\n\t"
+                   "s_mov_b64 exec, -1"
+                   : [x0] "+v"(x[0]), [x1] "+v"(x[1]), [x2] "+v"(x[2]), [x3] "+v"(x[3]), [x4] "+v"(x[4]),
+                     [x5] "+v"(x[5]), [x6] "+v"(x[6]), [q0] "+v"(q[0]), [q1] "+v"(q[1]), [q2] "+v"(q[2]),
+                     [q3] "+v"(q[3]), [q4] "+v"(q[4]), [q5] "+v"(q[5]), [q6] "+v"(q[6]), [i] "=&s"(i)
+                   : [np] "v"(np), [c] "s"(a.lf_c), [n] "s"(np_max)
+                   : "vcc", "scc");
+    }
+    double w[C];
+#pragma unroll
+    for (int e = 0; e < C; ++e) w[e] = __builtin_fma(a.lf_ch, q[e], -x[e]);
+    double m1l = rows_sumsq<C>(q, 0.0);
+    const double k1 = __builtin_fma(rows_sumsq<C>(w, 0.0), a.lf_idt2, m1l);
+    const double s2 = row_sum_l15(k1 - e0l);             // lane 15 of the row: 2 (E1 - E0)
+    const double se = row_sum_l15(e0l);                  // lane 15 of the row: 2 E0 - logc
+    E0 = __builtin_fma(se, 0.5, hlogc);
+    if (write_row) {
+      if (nbuf == 0) row_first = row;
+      Ebuf = park_row_shift(Ebuf, E0);
+      dEbuf = park_row_shift(dEbuf, E0 - Eprev);
+      if (++nbuf == kRowLanes) {
+        flush_E(kRowLanes);
+        nbuf = 0;
+      }
+    }
+    Eprev = E0;
+    if (it + 1 < a.it1) ring_momentum(it + 1);           // p (x) is dead: the next momentum goes into it
+    // the test in lane 15 of each row; the four bits widened to row masks on the SALU
+    const uint64_t b15 = (__builtin_amdgcn_ballot_w64(s2 < 0.0) | __builtin_amdgcn_ballot_w64(lnu < -s2)) &
+                         0x8000800080008000ull;
+    const uint64_t accm = (b15 << 1) - (b15 >> 15);
+    const uint64_t rej = ~accm;
+    if (rej != 0) {                                       // uniform; restores the rejecting rows under EXEC
+      uint64_t ex;
+      asm volatile("s_mov_b64 %[ex], exec\n\t"
+                   "s_mov_b64 exec, %[rej]\n\t"
+                   "v_mov_b64 %[q0], %[i0]\n\t"
+                   "v_mov_b64 %[q1], %[i1]\n\t"
+                   "v_mov_b64 %[q2], %[i2]\n\t"
+                   "v_mov_b64 %[q3], %[i3]\n\t"
+                   "v_mov_b64 %[q4], %[i4]\n\t"
+                   "v_mov_b64 %[q5], %[i5]\n\t"
+                   "v_mov_b64 %[q6], %[i6]\n\t"
+                   "v_mov_b64 %[m1], %[m0]\n\t"
+                   "s_mov_b64 exec, %[ex]"
+                   : [q0] "+v"(q[0]), [q1] "+v"(q[1]), [q2] "+v"(q[2]), [q3] "+v"(q[3]), [q4] "+v"(q[4]),
+                     [q5] "+v"(q[5]), [q6] "+v"(q[6]), [m1] "+v"(m1l), [ex] "=&s"(ex)
+                   : [rej] "s"(rej), [i0] "v"(qi[0]), [i1] "v"(qi[1]), [i2] "v"(qi[2]), [i3] "v"(qi[3]),
+                     [i4] "v"(qi[4]), [i5] "v"(qi[5]), [i6] "v"(qi[6]), [m0] "v"(m0l));
+    }
+    m0l = m1l;                                            // the potential part of the state kept
+    if (write_row && qcb && row >= a.q_row0) {
+      char* const rowb = qcb + (int64_t)qslot * a.D * 8;
+#pragma unroll
+      for (int j = 0; j < C; ++j)
+        if (j < C - 1 ? valid : st6)
+          __builtin_nontemporal_store(q[j], reinterpret_cast<double*>(rowb + qoff) + kRowLanes * j);
+    }
+    if (post) add_mask(n_acc, accm); else add_mask(n_acc_wu, accm);
+    add_mask(n_oob, it < a.i_oob ? rej : 0ull);
+    n_lf += (uint32_t)L;
+    n_lf2 += __umul24((uint32_t)L, (uint32_t)L);    // host: L_high < 2^12
+    e0l = rows_sumsq<C>(p, m0l);
+    if (post && ++phase == a.thin) {
+      phase = 0;
+      ++row;
+      if (++qslot == a.Lq) qslot = 0;
+    }
+  };
+  const int it_mid = min(max(a.wu, a.it0), a.it1);
+  for (int it = a.it0; it < it_mid; ++it) iteration(std::false_type{}, it);
+  for (int it = it_mid; it < a.it1; ++it) iteration(std::true_type{}, it);
+
+  if (nbuf > 0) flush_E(nbuf);
+#pragma unroll
+  for (int j = 0; j < C; ++j)
+    if (j < C - 1 ? valid : st6) qst[kRowLanes * j] = q[j];
+  if (valid && s == kRowLanes - 1) {                      // lane 15: where the row sums leave E
+    a.Eprev[c] = Eprev;
+    if (a.cnt) {
+      unsigned long long* cs = a.cnt + (c & (HMC_COUNTER_SLOTS - 1)) * HMC_NCOUNTERS;
+      if (n_acc) atomicAdd(cs + HMC_CNT_ACCEPT, (unsigned long long)n_acc);
+      if (n_acc_wu) atomicAdd(cs + HMC_CNT_ACCEPT_WU, (unsigned long long)n_acc_wu);
+      if (n_lf) atomicAdd(cs + HMC_CNT_LEAPFROG, (unsigned long long)n_lf);
+      if (n_lf2) atomicAdd(cs + HMC_CNT_LEAPFROG_SQ, (unsigned long long)n_lf2);
+      if (n_oob) atomicAdd(cs + HMC_CNT_OOB_REJECT, (unsigned long long)n_oob);
+    }
+  }
+}
+
+}  // namespace
+
+hipError_t launch_rows_iters(const RandArgs& a, hipStream_t s) {
+  // more than 64 KB of LDS: the limit is raised once per device
+  static bool raised[64] = {};
+  int dev = 0;
+  if (hipError_t e = hipGetDevice(&dev)) return e;
+  if (dev < 0 || dev >= 64 || !raised[dev]) {
+    if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rows_iters<7>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRowsLds))
+      return e;
+    if (dev >= 0 && dev < 64) raised[dev] = true;
+  }
+  constexpr int chains_per_block = (kRowsBlock / kWave) * kRowChains;
+  const dim3 grid((unsigned)((a.n + chains_per_block - 1) / chains_per_block));
+  k_rows_iters<7><<<grid, kRowsBlock, kRowsLds, s>>>(a);
+  return hipGetLastError();
+}
+
+}  // namespace hmc

@@ -219,7 +219,8 @@ def check(status, what=""):
 
 def random_layout(D, L_low, L_high):
     """hmc_random_layout for a diagonal target (host only): (K pairs per lane, lanes per chain,
-    chains per wave, 1 for the wave-per-chain kernels / 0 for the lane-group kernel)."""
+    chains per wave, 1 for the wave-per-chain kernels / 0 for the lane-group kernel and for the
+    four-chains-per-wave kernel of D = 97..112, which answers (4, 16, 4, 0))."""
     T = Target(D, HMC_TARGET_DIAG, None, None, 0.0)
     S = Schedule(0, 0, 1, 0, 1, 2, L_low, L_high, 1, 1, HMC_RNG_PHILOX, HMC_MODE_FAST, 10, 0, 0)
     out = (ctypes.c_int32 * 4)()
