@@ -195,8 +195,10 @@ hmc_status hmc_random_iters_ws(const hmc_target* t, const hmc_kinetic* k, const 
 
 /* Which form of the leapfrog hmc_random_iters runs for these arguments (host-side query, no
  * device access): 1 = the three-term recurrence u[n+1] = (2 - dt^2) u[n] - u[n-1] (FAST mode,
- * wave-per-chain kernels, identity precision and mass, scalar dt with 1e-3 <= |dt| < 2), 0 = the
- * kick/drift loops (every other case, EXACT mode included). */
+ * wave-per-chain kernels, identity precision and mass, scalar dt with 1e-3 <= |dt| < 2 and
+ * s->L_high * m <= 2e5 * |dt| * (1 - dt^2 / 4), m = 2 from dt^2 = 2 on and 1 below: the drift of
+ * the recurrence's phase over the longest trajectory stays below 5e-11 in q), 0 = the kick/drift
+ * loops (every other case, EXACT mode included). */
 int32_t hmc_random_leapfrog_form(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s);
 
 /* Which layout hmc_random_iters picks for a diagonal target (host only, no device access):
@@ -216,6 +218,13 @@ int32_t hmc_random_leapfrog_form(const hmc_target* t, const hmc_kinetic* k, cons
  * HMC_EINVAL for null arguments, D < 1 or L_low >= L_high; HMC_ENOTSUP for dense targets, the
  * large-D path, or no layout. */
 hmc_status hmc_random_layout(const hmc_target* t, const hmc_schedule* s, int32_t out[4]);
+
+/* The same query with the kinetic descriptor (k may be NULL: hmc_random_layout).  With it the
+ * four-chains-per-wave answer also requires what the launch requires of the mass and the step
+ * size: an identity mass and a scalar k->dt that hmc_random_leapfrog_form answers 1 for at
+ * s->L_high; otherwise the answer is the wave-per-chain layout the launch then takes. */
+hmc_status hmc_random_layout_ex(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s,
+                                int32_t out[4]);
 
 /* Record the size of a scratch buffer (hmc_state.order or a NUTS workspace) for the unsized entry
  * points: a later call that would need more than `bytes` returns HMC_EINVAL instead of writing past

@@ -88,6 +88,17 @@ def run_chains(q_start, P, Ls, lnu, dt, logc, form):
     return dict(q_chain=q_chain, E_chain=E_chain, accept=accept, traj0=traj0)
 
 
+def trajectory_deviation(dt, L, D=100, seed=0):
+    """dev[l], l = 0..L: max over steps 0..l and the D coordinates of |u_three_term - u_long_double|
+    on one trajectory from unit-normal q and p: the figure the host's bound on the trajectory length
+    is set from (dev[l] covers every trajectory of at most l steps)."""
+    rs = np.random.RandomState(seed)
+    q, p = rs.standard_normal(D), rs.standard_normal(D)
+    t3, _, _ = three_term(q, p, dt, L)
+    tl, _, _ = leapfrog_ld(q, p, dt, L)
+    return np.maximum.accumulate([float(np.max(np.abs(LD(a) - b))) for a, b in zip(t3, tl)])
+
+
 def energy_deviation(dtw, L=19, D=100, n=2000, seed=0):
     """max over n draws from the stationary law of |H_three_term - H_long_double| / H after L steps
     at dt * omega = dtw (H = (q.q + p.p) / 2): the figure the host's lower bound on dt is set from."""

@@ -6,6 +6,9 @@ and integrates the reference's kick-drift-kick in long double on the same tape. 
 itself shows against the long-double run on the test's own inputs, required to come out below
 1e-11 absolute (a ratio to the reference, never to the code under test).  The project's FAST
 contract against the oracle (q 1e-9, E 1e-10 relative, identical decisions) is asserted as well.
+The last tests run Philox schedules just inside and just outside the host's bound on the trajectory
+length against the oracle, after checking on the CPU that the oracle and the
+restatement are themselves within 1e-10 of the long-double run on those draws.
 """
 import ctypes
 
@@ -192,3 +195,107 @@ def test_fallback_two_fma_instance(dt):
     assert np.array_equal(_decisions(tape[0], q_chain), _decisions(tape[0], ref["q_chain"]))
     np.testing.assert_allclose(q_chain, ref["q_chain"], rtol=1e-9, atol=1e-9)
     np.testing.assert_allclose(eng.E_chain.cpu().numpy(), ref["E_chain"], rtol=1e-10)
+
+
+# ---- the bound on the trajectory length: L_high m <= 2e5 dt (1 - dt^2 / 4), m = 2
+# from dt^2 = 2 on.  (dt, L_low, the largest L_high inside the rule, iterations); L_high + 1 is the
+# schedule just outside.  Short trajectories at the lower bound on dt, thousands of steps on the
+# small-dt side, and thousands of steps near the stability limit, where the oracle in float64 is
+# itself still within 1e-10 of the long-double run (it is not at dt = 1.9999).
+EDGES = {"dt=1e-3": (1e-3, 190, 199, 8), "dt=1e-2": (1e-2, 1990, 1999, 3), "dt=1.99": (1.99, 1975, 1985, 3)}
+EDGE_N = 6
+
+
+def _edge_start(D, dt):
+    """Start points on the scale of the leapfrog orbit, 1 / sqrt(1 - dt^2 / 4) (10 at dt = 1.99: from
+    the target's own scale every proposal there is rejected and no long trajectory is ever kept)."""
+    scale = max(np.sqrt(2.0), 1.0 / np.sqrt(1.0 - 0.25 * dt * dt))
+    return np.random.RandomState(1000 + D).standard_normal((EDGE_N, D)) * scale
+
+
+def _edge_run(D, dt, lo, hi, niter, seed):
+    """One Philox run of 6 chains against the oracle on the host-regenerated draws, with the two
+    figures that make the reference side safe printed and asserted first: the float64 oracle and
+    the restatement of the three-term recurrence against the long-double run on these draws."""
+    from hmc_amd import _lib as H
+    from hmc_amd.engine import RandomEngine
+    from hmc_amd.target import MVNTarget
+    p0, P = wave_momenta(seed, EDGE_N, D, niter)
+    L, lnu = host_L_lnu(seed, np.arange(EDGE_N, dtype=np.uint64), niter, lo, hi)
+    q_start = _edge_start(D, dt)
+    ref = O.gen_sample_random(UnitCore(UnitMVN(D), dt), q_start, EDGE_N, niter, 1, 1, lo, hi,
+                              O.ReplayDraws(p0, P, L, lnu))
+    logc = D * np.log(2 * np.pi)
+    ld = M.run_chains(q_start, P, L, lnu, dt, logc, "long_double")
+    rest = M.run_chains(q_start, P, L, lnu, dt, logc, "three_term")
+    dev_oracle = float(np.max(np.abs(ref["q_chain"] - ld["q_chain"])))
+    dev_rest = float(np.max(np.abs(rest["q_chain"] - ld["q_chain"])))
+    form = H.random_leapfrog_form(D, lo, hi, dt)
+    print(f"D={D} dt={dt} L in [{lo}, {hi}): form {form}; against long double: oracle q {dev_oracle:.3e}, "
+          f"restatement q {dev_rest:.3e}; {int(ld['accept'].sum())} of {ld['accept'].size} accepted")
+    assert dev_oracle <= 1e-10
+    assert np.array_equal(_decisions(q_start, ref["q_chain"]), ld["accept"])
+    if form == 1:
+        assert dev_rest <= 1e-10 and np.array_equal(rest["accept"], ld["accept"])
+    eng = RandomEngine(MVNTarget(np.zeros(D), np.eye(D)), EDGE_N, niter, 1, 1, lo, hi, dt, rng="philox", seed=seed,
+                       fp_mode="fast")
+    assert _form(eng) == form
+    eng.init(q_start)
+    eng.run(1, niter + 1)
+    torch.cuda.synchronize()
+    c = eng.read_counters()
+    assert int(c[H.CNT_ACCEPT]) == ref["accept_count"] == int(ld["accept"].sum())
+    assert int(c[H.CNT_LEAPFROG]) == ref["n_leapfrog"] == int(L.sum())
+    assert int(c[H.CNT_LEAPFROG_SQ]) == int((L.astype(np.int64) ** 2).sum())
+    q_chain = eng.q_chain.cpu().numpy()
+    print(f"D={D}: GPU vs oracle: q {np.max(np.abs(q_chain - ref['q_chain'])):.3e}")
+    np.testing.assert_allclose(q_chain, ref["q_chain"], rtol=1e-9, atol=1e-9)
+    np.testing.assert_allclose(eng.E_chain.cpu().numpy(), ref["E_chain"], rtol=1e-10)
+    return form, ld["accept"]
+
+
+@pytest.mark.parametrize("side", ["inside", "outside"])
+@pytest.mark.parametrize("D", [100, 66])
+@pytest.mark.parametrize("edge", list(EDGES))
+def test_three_term_rule_edges(edge, D, side):
+    """Just inside the rule the three-term instance runs (at D = 100 the four-chain kernel, at
+    D = 66 the wave kernel's), just outside the two-FMA instance; both keep the FAST contract
+    against the oracle."""
+    from hmc_amd import _lib as H
+    dt, lo, hi, niter = EDGES[edge]
+    inside = side == "inside"
+    hi += 0 if inside else 1
+    assert H.random_leapfrog_form(D, lo, hi, dt) == (1 if inside else 0)
+    assert H.random_layout(D, lo, hi, dt=dt) == ((4, 16, 4, 0) if inside and D == 100 else (1, 64, 1, 1))
+    form, accept = _edge_run(D, dt, lo, hi, niter, 0xE0_0000 + D)
+    assert form == (1 if inside else 0)
+    assert accept.any()           # some long trajectory is kept: q rows that are not the start point
+
+
+def test_three_term_long_rows_equal_wave_kernel():
+    """Thousands of steps, inside the rule: the four-chain kernel and the wave-per-chain kernel
+    (taken with chain-0 capture requested) run the same FMAs per coordinate, so q and the q rows are
+    bitwise equal; E differs by the order of the energy sums."""
+    from hmc_amd import _lib as H
+    from hmc_amd.engine import RandomEngine
+    from hmc_amd.target import MVNTarget
+    D, seed = 100, 0xE3_0000
+    dt, lo, hi, niter = EDGES["dt=1e-2"]
+    assert H.random_layout(D, lo, hi, dt=dt) == (4, 16, 4, 0) and H.random_leapfrog_form(D, lo, hi, dt) == 1
+    q_start = _edge_start(D, dt)
+    out = []
+    for n_save in (2, 0):
+        eng = RandomEngine(MVNTarget(np.zeros(D), np.eye(D)), EDGE_N, niter, 1, 1, lo, hi, dt, rng="philox",
+                           seed=seed, fp_mode="fast", n_save=n_save)
+        assert _form(eng) == 1
+        eng.init(q_start)
+        eng.run(1, 3)
+        eng.run(3, niter + 1)
+        torch.cuda.synchronize()
+        out.append((eng.q.clone(), eng.q_chain.clone(), eng.E_chain.clone(), eng.read_counters()))
+    (qw, qcw, Ew, cw), (qr, qcr, Er, cr) = out
+    assert torch.equal(qw, qr) and torch.equal(qcw, qcr)
+    assert not torch.equal(qcr[:, 0], torch.as_tensor(q_start, device=qcr.device))
+    torch.testing.assert_close(Er, Ew, rtol=1e-12, atol=0)
+    for k in (H.CNT_ACCEPT, H.CNT_ACCEPT_WU, H.CNT_LEAPFROG, H.CNT_LEAPFROG_SQ):
+        assert cw[k] == cr[k]

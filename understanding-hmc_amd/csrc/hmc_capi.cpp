@@ -348,10 +348,15 @@ int32_t hmc_random_leapfrog_form(const hmc_target* t, const hmc_kinetic* k, cons
   if (lay.K == 0) return 0;
   hmc::RandArgs a{};
   a.dt = k->dt;
+  a.L_high = s->L_high;
   return hmc::leapfrog_three_term(a, lay, s->fp_mode == HMC_MODE_EXACT, general_diag(t, k)) ? 1 : 0;
 }
 
 hmc_status hmc_random_layout(const hmc_target* t, const hmc_schedule* s, int32_t out[4]) {
+  return hmc_random_layout_ex(t, nullptr, s, out);
+}
+
+hmc_status hmc_random_layout_ex(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, int32_t out[4]) {
   if (!t || !s || !out) return fail(HMC_EINVAL, "hmc_random_layout: null target/schedule/out");
   if (t->D < 1) return fail(HMC_EINVAL, "D must be >= 1");
   if (s->L_high <= s->L_low) return fail(HMC_EINVAL, "L_low must be < L_high (randint)");
@@ -361,9 +366,18 @@ hmc_status hmc_random_layout(const hmc_target* t, const hmc_schedule* s, int32_t
   if (lay.K == 0) return fail(HMC_ENOTSUP, "D=%d too large for the diagonal kernels", t->D);
   // 97 <= D <= 112, FAST, Philox, identity target: the four-chains-per-wave kernel (hmc_rows.hip)
   // takes the production launches (identity mass, scalar dt in the three-term range, no capture):
-  // 16 lanes per chain with 7 coordinates each, reported as ceil(7 / 2) pairs per lane
-  if (hmc::rows_shape(t->D, s->L_low, s->L_high) && s->fp_mode != HMC_MODE_EXACT && s->rng_mode != HMC_RNG_REPLAY &&
-      !t->q0 && !t->prec) {
+  // 16 lanes per chain with 7 coordinates each, reported as ceil(7 / 2) pairs per lane.  With a
+  // kinetic descriptor the mass and the three-term rule (dt against L_high) are checked as the
+  // launch checks them; without one they are taken as met.
+  bool rows = hmc::rows_shape(t->D, s->L_low, s->L_high) && s->fp_mode != HMC_MODE_EXACT &&
+              s->rng_mode != HMC_RNG_REPLAY && !t->q0 && !t->prec;
+  if (rows && k) {
+    hmc::RandArgs a{};
+    a.dt = k->dt;
+    a.L_high = s->L_high;
+    rows = hmc::leapfrog_three_term(a, lay, false, general_diag(t, k));
+  }
+  if (rows) {
     out[0] = 4;
     out[1] = 16;
     out[2] = 4;

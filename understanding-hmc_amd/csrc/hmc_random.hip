@@ -461,16 +461,29 @@ bool wave_layout(const Layout& lay) {
 // operation order keeps E within 1e-12 relative of a long-double integration over 19 steps at
 // D = 100 (tests/leapfrog_model.py energy_deviation; DESIGN.md 3.1: below 1e-12 from 4.6e-4 up,
 // the bound is set a factor 2 above that); upper bound: the integrator's stability limit
-// dt w = 2.  Outside the range the two-FMA loop runs.
+// dt w = 2.
+// Trajectory length: the rounded coefficient c = fl(2 - (dt w)^2) turns the phase by
+// (c - c_exact) / (2 sin theta) per step (cos theta = c / 2, sin theta = dt w sqrt(1 - (dt w)^2 / 4)),
+// and the orbit's amplitude is |p| / sqrt(1 - (dt w)^2 / 4), so after L steps q is off by about
+// |p| L |c - c_exact| / (2 dt w (1 - (dt w)^2 / 4)), with |c - c_exact| <= 2^-53 below (dt w)^2 = 2
+// and <= 2^-52 from there on ((dt w)^2 is rounded in [2, 4)).  The same model (max |q - q_ld| over
+// the trajectory at D = 100) stays below 2.2 x 2^-53 x L m / (dt w (1 - (dt w)^2 / 4)),
+// m = 1 or 2; the bound keeps that below 5e-11, half of the 1e-10 the routing test allows
+// (tests/test_leapfrog_form.py), i.e. a twentieth of FAST mode's 1e-9 on q.
+// Outside the range the two-FMA loop runs.
 // -DHMC_NO_THREE_TERM builds the library that never picks it (A/B).
 bool leapfrog_three_term(const RandArgs& a, const Layout& lay, bool exact, bool gen) {
 #ifdef HMC_NO_THREE_TERM
   return false;
 #else
   constexpr double kThreeTermMinDtw = 1e-3;
+  constexpr double kThreeTermMaxDrift = 2e5;   // L_high m / (dt w (1 - (dt w)^2 / 4)) at most
   if (exact || gen || !wave_layout(lay)) return false;
-  const double dtw2 = a.dt * a.dt;   // identity precision and mass: w = 1
-  return dtw2 >= kThreeTermMinDtw * kThreeTermMinDtw && dtw2 < 4.0;
+  const double dtw = a.dt < 0 ? -a.dt : a.dt;   // identity precision and mass: w = 1
+  const double dtw2 = dtw * dtw;
+  if (!(dtw2 >= kThreeTermMinDtw * kThreeTermMinDtw && dtw2 < 4.0)) return false;
+  const double m = dtw2 >= 2.0 ? 2.0 : 1.0;
+  return (double)a.L_high * m <= kThreeTermMaxDrift * dtw * (1.0 - 0.25 * dtw2);
 #endif
 }
 

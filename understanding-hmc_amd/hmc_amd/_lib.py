@@ -100,6 +100,8 @@ SYMBOLS = {
                                                   ctypes.POINTER(Schedule)]),
     "hmc_random_layout": (ctypes.c_int, [ctypes.POINTER(Target), ctypes.POINTER(Schedule),
                                          ctypes.POINTER(ctypes.c_int32 * 4)]),
+    "hmc_random_layout_ex": (ctypes.c_int, [ctypes.POINTER(Target), ctypes.POINTER(Kinetic),
+                                            ctypes.POINTER(Schedule), ctypes.POINTER(ctypes.c_int32 * 4)]),
     "hmc_workspace_register": (ctypes.c_int, [c_dp, ctypes.c_int64]),
     "hmc_stream_work_size": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int32, ctypes.c_int32]),
     "hmc_stream_accumulate": (ctypes.c_int, [c_dp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
@@ -217,15 +219,31 @@ def check(status, what=""):
     raise HMCError(text)
 
 
-def random_layout(D, L_low, L_high):
+def random_layout(D, L_low, L_high, dt=None):
     """hmc_random_layout for a diagonal target (host only): (K pairs per lane, lanes per chain,
     chains per wave, 1 for the wave-per-chain kernels / 0 for the lane-group kernel and for the
-    four-chains-per-wave kernel of D = 97..112, which answers (4, 16, 4, 0))."""
+    four-chains-per-wave kernel of D = 97..112, which answers (4, 16, 4, 0)).  With a scalar `dt`
+    (hmc_random_layout_ex, identity mass) the four-chain answer also depends on the three-term rule
+    for that step size and L_high, as the launch does."""
     T = Target(D, HMC_TARGET_DIAG, None, None, 0.0)
     S = Schedule(0, 0, 1, 0, 1, 2, L_low, L_high, 1, 1, HMC_RNG_PHILOX, HMC_MODE_FAST, 10, 0, 0)
     out = (ctypes.c_int32 * 4)()
-    check(lib().hmc_random_layout(ctypes.byref(T), ctypes.byref(S), ctypes.byref(out)), "hmc_random_layout")
+    if dt is None:
+        check(lib().hmc_random_layout(ctypes.byref(T), ctypes.byref(S), ctypes.byref(out)), "hmc_random_layout")
+    else:
+        K = Kinetic(None, None, None, float(dt), None, None, None)
+        check(lib().hmc_random_layout_ex(ctypes.byref(T), ctypes.byref(K), ctypes.byref(S), ctypes.byref(out)),
+              "hmc_random_layout_ex")
     return tuple(out)
+
+
+def random_leapfrog_form(D, L_low, L_high, dt):
+    """hmc_random_leapfrog_form for an identity target and mass in FAST mode with Philox draws
+    (host only): 1 for the three-term recurrence, 0 for the two-FMA loops."""
+    T = Target(D, HMC_TARGET_DIAG, None, None, 0.0)
+    K = Kinetic(None, None, None, float(dt), None, None, None)
+    S = Schedule(0, 0, 1, 0, 1, 2, L_low, L_high, 1, 1, HMC_RNG_PHILOX, HMC_MODE_FAST, 10, 0, 0)
+    return int(lib().hmc_random_leapfrog_form(ctypes.byref(T), ctypes.byref(K), ctypes.byref(S)))
 
 
 def ptr(t):
