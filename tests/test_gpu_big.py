@@ -132,6 +132,58 @@ def test_large_D_chain0_capture_vs_oracle(D, dense, fp_mode):
     np.testing.assert_allclose(eng.q_chain.cpu().numpy(), ref["q_chain"], rtol=1e-9, atol=1e-9)
 
 
+@pytest.mark.parametrize("fp_mode", ["exact", "fast"])
+def test_large_D_out_of_range_rejections_and_L_tallies(fp_mode):
+    """warm_up = 16 > L_chain * thin = 5: a rejection at i < i_oob = 11 writes q_chain row
+    (i - warm_up) // thin < -L_chain in the reference (samplers.py:471), an IndexError.  The tallies
+    of k_big_end (dense D = 136) over two calls, [1, 9) and [9, 21): the rejections before i_oob (from
+    the oracle's replay of the same draws with warm_up = 1, which stores every iteration: a rejected one
+    stores the point before it again, bit for bit), sum L and sum L^2 equal the reference's, and
+    HMC_sampler raises the reference's error.  dt = 0.5 makes the reference reject often."""
+    from hmc_amd import _lib as H
+    from hmc_amd.engine import RandomEngine
+    from hmc_amd.samplers import HMC_sampler
+    from hmc_amd.target import MVNTarget
+    D, N, Niter, wu, lo, hi, dt = 136, 3, 20, 16, 3, 9, 0.5
+    rs = np.random.RandomState(D + 9)
+    cov = O.mvn_cov(D, 0.5)
+    tgt = FastMVN(np.zeros(D), cov)
+    q_start = rs.standard_normal((N, D))
+    p0, P = rs.standard_normal((N, D)), rs.standard_normal((N, Niter, D))
+    Ls = rs.randint(lo, hi, size=(N, Niter)).astype(np.int32)
+    lnu = np.log(rs.random_sample((N, Niter)))
+
+    def oracle(warm_up):
+        return O.gen_sample_random(O.HMCCore(tgt, dt), q_start, N, Niter, warm_up, 1, lo, hi,
+                                   O.ReplayDraws(p0, P, Ls, lnu))
+    i_oob = wu - O.chain_len(Niter, wu, 1)
+    assert i_oob == 11
+    qc = oracle(1)["q_chain"]
+    rej = np.all(qc == np.concatenate([q_start[:, None], qc[:, :-1]], axis=1), axis=2)[:, :i_oob - 1]
+    n_oob = int(rej.sum())
+    assert 0 < n_oob < rej.size                         # the reference rejects there, but not always
+    with pytest.raises(IndexError):
+        oracle(wu)
+    target = MVNTarget(np.zeros(D), cov, logdet_const=tgt.c)
+    eng = RandomEngine(target, N, Niter, wu, 1, lo, hi, dt, rng="replay", fp_mode=fp_mode)
+    assert eng._order is not None            # the large-D workspace
+    eng.set_replay(p0, P, Ls, lnu)
+    eng.init(q_start)
+    eng.run(1, 9)
+    eng.run(9, Niter + 1)
+    torch.cuda.synchronize()
+    cnt = eng.read_counters()
+    L = Ls.astype(np.int64)
+    assert int(cnt[H.CNT_OOB_REJECT]) == n_oob
+    assert int(cnt[H.CNT_LEAPFROG]) == int(L.sum()) and int(cnt[H.CNT_LEAPFROG_SQ]) == int((L * L).sum())
+    if fp_mode == "fast":
+        h = HMC_sampler(D, None, None, Nchain=N, Niter=Niter, sampler_type="Random", L_low=lo, L_high=hi, dt=dt,
+                        warm_up_num=wu, target=target, fp_mode=fp_mode)
+        h.set_random_replay(p0, P, Ls, lnu)
+        with pytest.raises(IndexError):
+            h.gen_sample(q_start, verbose=False)
+
+
 @pytest.mark.parametrize("D,rho,dense,full_p", [(160, 0.8, True, False), (2100, 0.0, False, False),
                                                (160, 0.8, True, True)])
 def test_large_D_philox_stationary(D, rho, dense, full_p):

@@ -29,9 +29,13 @@ CASES = {
     "F": (128, 100, 3, 10, 0, 1, 5, 12, 0.8, 1, False, False),      # ABI limit in D
 }
 
+# warm_up = 16 > L_chain * thin = 5: the reference raises IndexError
+# (test_poisson_out_of_range_rejections_and_L_tallies); 19 chains are two tiles, the second with three
+OOB_CASE = (3, 8, 19, 20, 16, 1, 5, 20, 1.5, 1, False, False)
+
 
 def recipe(name, family="poisson", N=None, Niter=None):
-    D, n, N_, Niter_, wu, thin, Llo, Lhi, cdt, seed, dtvec, covp = CASES[name]
+    D, n, N_, Niter_, wu, thin, Llo, Lhi, cdt, seed, dtvec, covp = OOB_CASE if name == "oob" else CASES[name]
     N, Niter = N or N_, Niter or Niter_
     c = G.recipe(family, D, n, N, cdt, seed, dtvec=dtvec, covp=covp)
     rs = c["rs"]
@@ -224,3 +228,36 @@ def test_one_overflowing_chain_is_rejected_and_isolated():
     assert np.all(mixed.q_chain[15] == bad[0])
     assert (mixed._acc, mixed._acc_wu) == (ok._acc, ok._acc_wu)        # every proposal of the bad chain rejected
     assert not np.any(np.isfinite(mixed.E_chain[15]))
+
+
+# ------------------------------------------------------------------------------------------ 7
+def test_poisson_out_of_range_rejections_and_L_tallies():
+    """A rejection at i < i_oob = warm_up - L_chain * thin = 11 writes q_chain row
+    (i - warm_up) // thin < -L_chain in the reference (samplers.py:471), an IndexError.  The tallies
+    of the Poisson instance of k_logit_iters over two launches, [1, 9) and [9, 21): the rejections
+    before i_oob (from the oracle's replay of the same draws with warm_up = 1; the decisions do not
+    depend on warm_up), sum L and sum L^2 equal the reference's, and HMC_sampler raises the reference's
+    error."""
+    from hmc_amd import _lib as H
+    from hmc_amd.engine import GLMEngine
+    c = recipe("oob")
+    i_oob = c["wu"] - O.chain_len(c["Niter"], c["wu"], c["thin"])
+    assert i_oob == 11
+    dE = oracle_run(dict(c, wu=1))["dE_prop"][:, :i_oob - 1]
+    n_oob = int(np.sum(~((dE < 0) | (c["lnu"][:, :i_oob - 1] < -dE))))
+    assert 0 < n_oob < dE.size                          # the reference rejects there, but not always
+    with pytest.raises(IndexError):
+        oracle_run(c)
+    eng = GLMEngine(G.glm_target(c), c["N"], c["Niter"], c["wu"], c["thin"], c["Llo"], c["Lhi"], c["dt"],
+                    rng="replay")
+    eng.set_replay(c["p0"], c["P"], c["L"], c["lnu"])
+    eng.init(c["q_start"])
+    eng.run(1, 9)
+    eng.run(9, c["Niter"] + 1)
+    torch.cuda.synchronize()
+    cnt = eng.read_counters()
+    L = c["L"].astype(np.int64)
+    assert int(cnt[H.CNT_OOB_REJECT]) == n_oob
+    assert int(cnt[H.CNT_LEAPFROG]) == int(L.sum()) and int(cnt[H.CNT_LEAPFROG_SQ]) == int((L * L).sum())
+    with pytest.raises(IndexError):
+        sampler(c).gen_sample(c["q_start"], verbose=False)

@@ -277,3 +277,53 @@ def test_circular_window_on_a_k2_layout():
     cnt = eng.read_counters()
     assert int(cnt[H.CNT_ACCEPT]) == ref["accept_count"] and int(cnt[H.CNT_ACCEPT_WU]) == ref["accept_count_warm_up"]
     assert int(cnt[H.CNT_LEAPFROG]) == ref["n_leapfrog"] == int(c["L"].sum())
+
+
+# ------------------------------------------------------------------------------------------ f
+@functools.lru_cache(maxsize=None)
+def oob_case():
+    """warm_up = 16 > L_chain * thin = 5 on the (1, 2, 32) layout: 37 chains are a full wave and five
+    chains of a second one.  A rejection at i < i_oob = warm_up - L_chain * thin = 11 writes q_chain
+    row (i - warm_up) // thin < -L_chain in the reference (samplers.py:471), an IndexError.  dt = 1.3
+    makes the unit target reject often.  Returns the inputs and the (N, Niter) rejections, read from the
+    oracle's replay of the same draws with warm_up = 1, which stores every iteration (a rejected
+    iteration stores the point before it again, bit for bit; the decisions do not depend on warm_up)."""
+    D, lo, hi, N, Niter = 3, 3, 9, 37, 20
+    assert layout(D, lo, hi) == (1, 2, 32)
+    rs = np.random.RandomState(3037)
+    c = dict(_problem(D, False, rs), dt=1.3)
+    c.update(D=D, N=N, Niter=Niter, wu=16, thin=1, lo=lo, hi=hi, offset=0, q_start=rs.standard_normal((N, D)),
+             p0=rs.standard_normal((N, D)), P=rs.standard_normal((N, Niter, D)),
+             L=rs.randint(lo, hi, size=(N, Niter)).astype(np.int32), lnu=np.log(rs.random_sample((N, Niter))))
+    qc = _oracle(dict(c, wu=1))["q_chain"]
+    return c, np.all(qc == np.concatenate([c["q_start"][:, None], qc[:, :-1]], axis=1), axis=2)
+
+
+@pytest.mark.parametrize("fp_mode", ["exact", "fast"])
+def test_out_of_range_rejections_and_L_tallies(fp_mode):
+    """The tallies of k_random_iters over two launches, [1, 9) and [9, 21): the rejections before
+    i_oob, sum L and sum L^2 equal the reference's, and HMC_sampler raises the reference's error."""
+    from hmc_amd import _lib as H
+    from hmc_amd.engine import RandomEngine
+    from hmc_amd.target import MVNTarget
+    c, rej = oob_case()
+    i_oob = c["wu"] - O.chain_len(c["Niter"], c["wu"], 1)
+    assert i_oob == 11
+    n_oob = int(rej[:, :i_oob - 1].sum())
+    assert 0 < n_oob < rej[:, :i_oob - 1].size          # the reference rejects there, but not always
+    with pytest.raises(IndexError):
+        _oracle(c)
+    eng = RandomEngine(MVNTarget(c["q0"], c["cov0"]), c["N"], c["Niter"], c["wu"], 1, c["lo"], c["hi"], c["dt"],
+                       rng="replay", fp_mode=fp_mode)
+    eng.set_replay(c["p0"], c["P"], c["L"], c["lnu"])
+    eng.init(c["q_start"])
+    eng.run(1, 9)
+    eng.run(9, c["Niter"] + 1)
+    torch.cuda.synchronize()
+    cnt = eng.read_counters()
+    L = c["L"].astype(np.int64)
+    assert int(cnt[H.CNT_OOB_REJECT]) == n_oob
+    assert int(cnt[H.CNT_LEAPFROG]) == int(L.sum()) and int(cnt[H.CNT_LEAPFROG_SQ]) == int((L * L).sum())
+    if fp_mode == "fast":
+        with pytest.raises(IndexError):
+            run(c, fp_mode)

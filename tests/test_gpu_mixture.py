@@ -71,11 +71,15 @@ CASES = {
     "H": (512, 8, 2, 10, 0, 1, 5, 12, 0.3, 8, 5, False, False),    # ABI limit
 }
 
+# warm_up = 16 > L_chain * thin = 5: the reference raises IndexError (test_out_of_range_rejections_and_L_tallies);
+# 37 chains on the (1, 2, 32) lane-group layout are a full wave and five chains of a second one
+OOB_CASE = (3, 2, 37, 20, 16, 1, 5, 20, 0.9, 12, 3, False, False)
+
 
 def recipe(name, N=None, Niter=None):
     """The shared input recipe, every draw from one RandomState(seed) in this order: weights,
     means, variances, start points, Z0, Z, L, log u, then the optional dt vector and cov_p."""
-    D, K, N_, Niter_, wu, thin, Llo, Lhi, dt, seed, sep, dtvec, covp = CASES[name]
+    D, K, N_, Niter_, wu, thin, Llo, Lhi, dt, seed, sep, dtvec, covp = OOB_CASE if name == "oob" else CASES[name]
     N, Niter = N or N_, Niter or Niter_
     rs = np.random.RandomState(seed)
     w = rs.uniform(0.5, 1.5, K)
@@ -376,3 +380,35 @@ def test_refusals_and_mvn_unchanged():
     after = mvn()
     for a in ("q_chain", "E_chain", "dE_chain", "_acc", "n_leapfrog"):
         assert np.array_equal(getattr(before, a), getattr(after, a)), a
+
+
+# ------------------------------------------------------------------------------------------ 11
+def test_out_of_range_rejections_and_L_tallies():
+    """A rejection at i < i_oob = warm_up - L_chain * thin = 11 writes q_chain row
+    (i - warm_up) // thin < -L_chain in the reference (samplers.py:471), an IndexError.  The tallies
+    of k_mix_iters over two launches, [1, 9) and [9, 21): the rejections before i_oob (from the
+    oracle's replay of the same draws with warm_up = 1; the decisions do not depend on warm_up), sum L
+    and sum L^2 equal the reference's, and HMC_sampler raises the reference's error."""
+    from hmc_amd import _lib as H
+    from hmc_amd.engine import MixtureEngine
+    c = recipe("oob")
+    i_oob = c["wu"] - O.chain_len(c["Niter"], c["wu"], c["thin"])
+    assert i_oob == 11
+    dE = oracle_run(dict(c, wu=1))["dE_prop"][:, :i_oob - 1]
+    n_oob = int(np.sum(~((dE < 0) | (c["lnu"][:, :i_oob - 1] < -dE))))
+    assert 0 < n_oob < dE.size                          # the reference rejects there, but not always
+    with pytest.raises(IndexError):
+        oracle_run(c)
+    eng = MixtureEngine(target_of(c), c["N"], c["Niter"], c["wu"], c["thin"], c["Llo"], c["Lhi"], c["dt"],
+                        rng="replay")
+    eng.set_replay(c["p0"], c["P"], c["L"], c["lnu"])
+    eng.init(c["q_start"])
+    eng.run(1, 9)
+    eng.run(9, c["Niter"] + 1)
+    torch.cuda.synchronize()
+    cnt = eng.read_counters()
+    L = c["L"].astype(np.int64)
+    assert int(cnt[H.CNT_OOB_REJECT]) == n_oob
+    assert int(cnt[H.CNT_LEAPFROG]) == int(L.sum()) and int(cnt[H.CNT_LEAPFROG_SQ]) == int((L * L).sum())
+    with pytest.raises(IndexError):
+        sampler(c).gen_sample(c["q_start"], verbose=False)

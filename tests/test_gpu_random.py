@@ -461,3 +461,64 @@ def test_dense_checkpoint_resume_bitexact(tmp_path):
         a_.run(a, a + 1)
     torch.cuda.synchronize()
     assert torch.equal(a_.q_chain, ref.q_chain)
+
+
+def _oob_case(D, rho, N):
+    """Niter = 20, warm_up = 16, thin = 1 (L_chain = 5): a rejection at i < i_oob = 11 writes q_chain
+    row (i - warm_up) // thin < -L_chain in the reference (samplers.py:471), an IndexError.  dt = 1.1
+    (rho = None: the unit target) or 0.9 makes the reference reject often.  Returns the inputs and the
+    (N, Niter) rejections, read from the oracle's replay of the same draws with warm_up = 1, which
+    stores every iteration (a rejected one stores the point before it again, bit for bit)."""
+    rs = np.random.RandomState(1000 * D + N)
+    Niter, lo, hi = 20, 3, 9
+    c = dict(D=D, N=N, Niter=Niter, wu=16, lo=lo, hi=hi, dt=1.1 if rho is None else 0.9,
+             cov=np.eye(D) if rho is None else O.mvn_cov(D, rho), q_start=rs.standard_normal((N, D)),
+             p0=rs.standard_normal((N, D)), P=rs.standard_normal((N, Niter, D)),
+             L=rs.randint(lo, hi, size=(N, Niter)).astype(np.int32), lnu=np.log(rs.random_sample((N, Niter))))
+    qc = _oob_oracle(c, 1)["q_chain"]
+    return c, np.all(qc == np.concatenate([c["q_start"][:, None], qc[:, :-1]], axis=1), axis=2)
+
+
+def _oob_oracle(c, wu):
+    return O.gen_sample_random(O.HMCCore(O.MVNTarget(np.zeros(c["D"]), c["cov"]), c["dt"]), c["q_start"], c["N"],
+                               c["Niter"], wu, 1, c["lo"], c["hi"], O.ReplayDraws(c["p0"], c["P"], c["L"], c["lnu"]))
+
+
+@pytest.mark.parametrize("fp_mode", ["exact", "fast"])
+@pytest.mark.parametrize("D,rho,N", [(66, None, 5), (5, 0.5, 19)], ids=["wave", "dense"])
+def test_out_of_range_rejections_and_L_tallies(D, rho, N, fp_mode):
+    """The tallies of the wave-per-chain kernel (D = 66: hmc_wave.hip, below the four-chain kernel's
+    range) and of k_dense_iters (19 chains: two tiles, the second with three) over two launches,
+    [1, 9) and [9, 21): the rejections before i_oob, sum L and sum L^2 equal the reference's, and
+    HMC_sampler (L-ordered tiles for the dense target: one launch per iteration) raises its error."""
+    from hmc_amd import _lib as H
+    from hmc_amd.engine import RandomEngine
+    from hmc_amd.samplers import HMC_sampler
+    from hmc_amd.target import MVNTarget
+    c, rej = _oob_case(D, rho, N)
+    i_oob = c["wu"] - O.chain_len(c["Niter"], c["wu"], 1)
+    assert i_oob == 11
+    n_oob = int(rej[:, :i_oob - 1].sum())
+    assert 0 < n_oob < rej[:, :i_oob - 1].size          # the reference rejects there, but not always
+    with pytest.raises(IndexError):
+        _oob_oracle(c, c["wu"])
+    if rho is None:
+        assert H.random_layout(D, c["lo"], c["hi"]) == (1, 64, 1, 1)
+    target = MVNTarget(np.zeros(D), c["cov"])
+    eng = RandomEngine(target, N, c["Niter"], c["wu"], 1, c["lo"], c["hi"], c["dt"], rng="replay", fp_mode=fp_mode,
+                       order_tiles=False)
+    eng.set_replay(c["p0"], c["P"], c["L"], c["lnu"])
+    eng.init(c["q_start"])
+    eng.run(1, 9)
+    eng.run(9, c["Niter"] + 1)
+    torch.cuda.synchronize()
+    cnt = eng.read_counters()
+    L = c["L"].astype(np.int64)
+    assert int(cnt[H.CNT_OOB_REJECT]) == n_oob
+    assert int(cnt[H.CNT_LEAPFROG]) == int(L.sum()) and int(cnt[H.CNT_LEAPFROG_SQ]) == int((L * L).sum())
+    if fp_mode == "fast":
+        h = HMC_sampler(D, None, None, Nchain=N, Niter=c["Niter"], sampler_type="Random", L_low=c["lo"],
+                        L_high=c["hi"], dt=c["dt"], warm_up_num=c["wu"], target=target, fp_mode=fp_mode)
+        h.set_random_replay(c["p0"], c["P"], c["L"], c["lnu"])
+        with pytest.raises(IndexError):
+            h.gen_sample(c["q_start"], verbose=False)

@@ -22,7 +22,7 @@
 #include "hmc_device.hpp"
 #include "hmc_internal.hpp"
 #include "hmc_dense_ops.hpp"
-#include "hmc_nuts_tree.hpp"   // stores_row: the row rule shared with the NUTS kernels
+#include "hmc_random_iter.hpp"
 
 namespace hmc {
 
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void k_big_begin(BigArgs b, int it) {
   const double E0 = 0.5 * (a.logc + (maha + kin));
   if (lane == 0) {
     if (!MASS && stores_row(a, it)) {                             // (full cov_p: k_big_energy)
-      const int64_t row = c * (int64_t)a.Lc + (it - a.wu) / a.thin;
+      const int64_t row = c * (int64_t)a.Lc + row_of(a, it);
       if (a.Ec) a.Ec[row] = E0;
       if (a.dEc) a.dEc[row] = E0 - a.Eprev[c];
     }
@@ -110,10 +110,9 @@ __global__ __launch_bounds__(256) void k_big_begin(BigArgs b, int it) {
       L = a.rL[c * (int64_t)a.niter + (it - 1)];
       lnu = a.rlnu[c * (int64_t)a.niter + (it - 1)];
     } else {
-      const uint4 r = draw_block(kDrawSlot, (uint32_t)it, gc, a.k0, a.k1);
-      L = uniform_int(r.x, a.L_low, a.L_high);
-      const double u = u53(r.z, r.w);
-      lnu = u > 0.0 ? fast_log(u) : -__builtin_inf();
+      const TrajDraw d = draw_traj(a, it, gc);
+      L = d.L;
+      lnu = d.lnu;
     }
     b.L[c] = L;
     b.lnu[c] = lnu;
@@ -231,7 +230,7 @@ __global__ __launch_bounds__(256) void k_big_end(BigArgs b, int it) {
   const bool accept = (dE < 0.0) || (lnu < -dE);                    // :462
   const bool post = it >= a.wu;
   const bool write_row = stores_row(a, it);
-  const int64_t row = post ? (int64_t)((it - a.wu) / a.thin) : 0;
+  const int64_t row = row_of(a, it);
   const bool store = write_row && a.qc && row >= a.q_row0;
   double* rowp = store ? a.qc + c * (int64_t)a.Lq * D + (row % a.Lq) * D : nullptr;
   for (int d = lane; d < D; d += kWave) {
@@ -282,7 +281,7 @@ __global__ __launch_bounds__(256) void k_big_energy(BigArgs b, int it) {
     if (a.dEc) a.dEc[c * (int64_t)a.Lc] = 0.0;
   } else {
     if (stores_row(a, it)) {
-      const int64_t row = c * (int64_t)a.Lc + (it - a.wu) / a.thin;
+      const int64_t row = c * (int64_t)a.Lc + row_of(a, it);
       if (a.Ec) a.Ec[row] = E0;
       if (a.dEc) a.dEc[row] = E0 - a.Eprev[c];
     }
@@ -352,12 +351,7 @@ __global__ __launch_bounds__(256) void k_big_init(BigArgs b) {
   }
   maha = wave_sum_dpp(maha);
   kin = wave_sum_dpp(kin);
-  if (lane == 0) {
-    const double E0 = 0.5 * (a.logc + (maha + kin));
-    a.Eprev[c] = E0;
-    if (a.Ec) a.Ec[c * (int64_t)a.Lc] = E0;
-    if (a.dEc) a.dEc[c * (int64_t)a.Lc] = 0.0;
-  }
+  if (lane == 0) store_init_energy(a, c, 0.5 * (a.logc + (maha + kin)));
 }
 
 dim3 waves_grid(int64_t waves) { return dim3((unsigned)((waves + 3) / 4)); }

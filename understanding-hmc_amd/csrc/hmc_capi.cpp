@@ -84,6 +84,56 @@ hmc_status check_mass(const hmc_target* t, const hmc_kinetic* k, const hmc_sched
   return HMC_OK;
 }
 
+hmc_status check_iter_range(const hmc_schedule* s) {
+  if (s->iter_begin < 1 || s->iter_end < s->iter_begin || s->iter_end > s->n_iter + 1)
+    return fail(HMC_EINVAL, "iteration range must satisfy 1 <= begin <= end <= Niter+1");
+  return HMC_OK;
+}
+
+// What the chain-init entries (MVN, mixture, GLM) check alike once the target and the schedule have
+// passed.  *run: there are chains to initialise; HMC_OK without it is the entry's answer (empty batch).
+hmc_status check_chain_init(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
+                            const double* q_start, const hmc_state* st, bool* run) {
+  *run = false;
+  if (!st) return fail(HMC_EINVAL, "null state");
+  if (hmc_status e = check_mass(t, k, s)) return e;
+  if (s->n_chains == 0) return HMC_OK;   // empty batch: zero-size buffers may be NULL
+  if (!st->q || !st->E_prev || !q_start) return fail(HMC_EINVAL, "null state/q_start");
+  if (s->rng_mode == HMC_RNG_REPLAY && (!r || !r->p0)) return fail(HMC_EINVAL, "replay mode needs p0");
+  *run = true;
+  return HMC_OK;
+}
+
+// The trajectory range a lane-group layout is chosen for at chain init: the schedule's, or the
+// reference's default (5, 20) when the caller left it unset (init draws no trajectory length).
+struct TrajRange {
+  int lo, hi;
+};
+TrajRange init_traj_range(const hmc_schedule* s) {
+  return s->L_high > s->L_low ? TrajRange{s->L_low, s->L_high} : TrajRange{5, 20};
+}
+
+// What the Random iteration entries (MVN, mixture, GLM) check alike once the target and the schedule
+// have passed, in the order the entries have always checked it.  *run: there is something to launch;
+// HMC_OK without it is the entry's answer (empty batch or empty iteration range).
+hmc_status check_random_iters(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
+                              const hmc_state* st, bool* run) {
+  *run = false;
+  if (!st) return fail(HMC_EINVAL, "null state");
+  if (hmc_status e = check_window(t, s, st)) return e;
+  if (hmc_status e = check_mass(t, k, s)) return e;
+  if (hmc_status e = check_iter_range(s)) return e;
+  if (s->n_chains == 0) return HMC_OK;   // empty batch: zero-size buffers may be NULL
+  if (!st->q || !st->E_prev) return fail(HMC_EINVAL, "null state");
+  if (s->rng_mode == HMC_RNG_REPLAY && (!r || !r->p || !r->L || !r->lnu))
+    return fail(HMC_EINVAL, "replay mode needs p, L, lnu");
+  if (s->iter_end == s->iter_begin) return HMC_OK;
+  if (st->n_save > 0 && st->traj_q && st->traj_stride < s->L_high)
+    return fail(HMC_EINVAL, "traj_stride must be >= L_high");
+  *run = true;
+  return HMC_OK;
+}
+
 hmc::RandArgs rand_args(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
                         hmc_state* st, const hmc::Layout& lay) {
   hmc::RandArgs a{};
@@ -162,6 +212,25 @@ bool general_diag(const hmc_target* t, const hmc_kinetic* k) {
   return t->q0 || t->prec || k->minv || k->p_scale || k->dt_vec;
 }
 
+// rand_args plus what the NUTS kernels take: the tree's depth limit, the workspace, the replay tape;
+// no chain-0 capture (the reference never fills it for NUTS)
+hmc::RandArgs nuts_args(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
+                        hmc_state* st, int D, void* workspace) {
+  const bool replay = s->rng_mode == HMC_RNG_REPLAY;
+  const hmc::Layout lay{0, 0, 16, (D + 1) / 2};   // 16 chain slots per wave (debug stamps: one row per wave)
+  hmc::RandArgs a = rand_args(t, k, s, replay ? r : nullptr, st, lay);
+  a.d_max = s->d_max;
+  a.on_dmax = s->on_dmax;
+  a.ws = static_cast<double*>(workspace);
+  if (replay) {
+    a.tape = r->tape;
+    a.tape_stride = r->tape_stride;
+  }
+  a.traj_q = nullptr;
+  a.n_save = 0;
+  return a;
+}
+
 constexpr int32_t kMaxLags = 1 << 20;   // lag passes of the diagnostics (any n the samples allow)
 
 // Host-side record of the scratch buffers' sizes (device pointer -> bytes): the sized entries
@@ -224,12 +293,9 @@ const char* hmc_last_error(void) { return g_err.c_str(); }
 hmc_status hmc_chain_init(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
                           const double* q_start, hmc_state* st, void* stream) {
   if (hmc_status e = check_schedule(t, k, s, false)) return e;
-  if (!st) return fail(HMC_EINVAL, "null state");
-  if (hmc_status e = check_mass(t, k, s)) return e;
-  if (s->n_chains == 0) return HMC_OK;   // empty batch: zero-size buffers may be NULL
-  if (!st->q || !st->E_prev || !q_start) return fail(HMC_EINVAL, "null state/q_start");
+  bool run;
+  if (hmc_status e = check_chain_init(t, k, s, r, q_start, st, &run); e != HMC_OK || !run) return e;
   const bool replay = s->rng_mode == HMC_RNG_REPLAY;
-  if (replay && (!r || !r->p0)) return fail(HMC_EINVAL, "replay mode needs p0");
   if (hmc_status e = ws_check(st->order, order_need(t, k, s, st), "hmc_chain_init: state.order")) return e;
   const bool dense = t->kind == HMC_TARGET_DENSE;
   if (hmc::big_path(dense, t->D)) {   // large D: chain state in the workspace (hmc_big.hip)
@@ -252,8 +318,8 @@ hmc_status hmc_chain_init(const hmc_target* t, const hmc_kinetic* k, const hmc_s
     }
     return hip_status(hmc::launch_dense_init(a, replay, (hipStream_t)stream), "hmc_chain_init(dense)");
   }
-  const int L_lo = s->L_high > s->L_low ? s->L_low : 5, L_hi = s->L_high > s->L_low ? s->L_high : 20;
-  const hmc::Layout lay = hmc::choose_layout(t->D, L_lo, L_hi);
+  const TrajRange L = init_traj_range(s);
+  const hmc::Layout lay = hmc::choose_layout(t->D, L.lo, L.hi);
   if (lay.K == 0) return fail(HMC_ENOTSUP, "D=%d too large for the diagonal kernels", t->D);
   hmc::RandArgs a = rand_args(t, k, s, replay ? r : nullptr, st, lay);
   a.qstart = q_start;
@@ -264,18 +330,9 @@ hmc_status hmc_chain_init(const hmc_target* t, const hmc_kinetic* k, const hmc_s
 hmc_status hmc_random_iters(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
                             hmc_state* st, void* stream) {
   if (hmc_status e = check_schedule(t, k, s, true)) return e;
-  if (!st) return fail(HMC_EINVAL, "null state");
-  if (hmc_status e = check_window(t, s, st)) return e;
-  if (hmc_status e = check_mass(t, k, s)) return e;
-  if (s->iter_begin < 1 || s->iter_end < s->iter_begin || s->iter_end > s->n_iter + 1)
-    return fail(HMC_EINVAL, "iteration range must satisfy 1 <= begin <= end <= Niter+1");
-  if (s->n_chains == 0) return HMC_OK;   // empty batch: zero-size buffers may be NULL
-  if (!st->q || !st->E_prev) return fail(HMC_EINVAL, "null state");
+  bool run;
+  if (hmc_status e = check_random_iters(t, k, s, r, st, &run); e != HMC_OK || !run) return e;
   const bool replay = s->rng_mode == HMC_RNG_REPLAY;
-  if (replay && (!r || !r->p || !r->L || !r->lnu)) return fail(HMC_EINVAL, "replay mode needs p, L, lnu");
-  if (s->n_chains == 0 || s->iter_end == s->iter_begin) return HMC_OK;
-  if (st->n_save > 0 && st->traj_q && st->traj_stride < s->L_high)
-    return fail(HMC_EINVAL, "traj_stride must be >= L_high");
   if (hmc_status e = ws_check(st->order, order_need(t, k, s, st), "hmc_random_iters: state.order")) return e;
   const bool dense = t->kind == HMC_TARGET_DENSE;
   if (hmc::big_path(dense, t->D)) {   // large D (hmc_big.hip)
@@ -488,8 +545,7 @@ hmc_status hmc_nuts_iters(const hmc_target* t, const hmc_kinetic* k, const hmc_s
   if (hmc_status e = check_schedule(t, k, s, false)) return e;
   if (!st) return fail(HMC_EINVAL, "null state");
   if (hmc_status e = check_window(t, s, st)) return e;
-  if (s->iter_begin < 1 || s->iter_end < s->iter_begin || s->iter_end > s->n_iter + 1)
-    return fail(HMC_EINVAL, "iteration range must satisfy 1 <= begin <= end <= Niter+1");
+  if (hmc_status e = check_iter_range(s)) return e;
   if (s->n_chains == 0) return HMC_OK;   // empty batch: zero-size buffers may be NULL
   if (!st->q || !st->E_prev) return fail(HMC_EINVAL, "null state");
   if (s->d_max < 1 || s->d_max > hmc::kNutsDmaxMax) return fail(HMC_EINVAL, "d_max must be in [1, %d]", hmc::kNutsDmaxMax);
@@ -504,17 +560,7 @@ hmc_status hmc_nuts_iters(const hmc_target* t, const hmc_kinetic* k, const hmc_s
     if (need < 0) return fail(HMC_EINVAL, "NUTS workspace: unsupported D=%d / d_max=%d", t->D, s->d_max);
     if (hmc_status e = ws_check(workspace, need, "hmc_nuts_iters: workspace")) return e;
   }
-  const hmc::Layout lay{0, 0, 16, (t->D + 1) / 2};   // 16 chain slots per wave (debug stamps: one row per wave)
-  hmc::RandArgs a = rand_args(t, k, s, replay ? r : nullptr, st, lay);
-  a.d_max = s->d_max;
-  a.on_dmax = s->on_dmax;
-  a.ws = static_cast<double*>(workspace);
-  if (replay) {
-    a.tape = r->tape;
-    a.tape_stride = r->tape_stride;
-  }
-  a.traj_q = nullptr;
-  a.n_save = 0;
+  const hmc::RandArgs a = nuts_args(t, k, s, r, st, t->D, workspace);
   const bool exact = s->fp_mode == HMC_MODE_EXACT;
   switch (hmc::nuts_kernel(t->D)) {
     case hmc::NutsKernel::Lock:
@@ -623,13 +669,11 @@ hmc_status hmc_mix_chain_init(const hmc_mixture* m, const hmc_kinetic* k, const 
   if (hmc_status e = check_mixture(m, k, "hmc_mix_chain_init")) return e;
   const hmc_target t = mix_shape(m);
   if (hmc_status e = check_schedule(&t, k, s, false)) return e;
-  if (!st) return fail(HMC_EINVAL, "null state");
-  if (s->n_chains == 0) return HMC_OK;   // empty batch: zero-size buffers may be NULL
-  if (!st->q || !st->E_prev || !q_start) return fail(HMC_EINVAL, "null state/q_start");
+  bool run;
+  if (hmc_status e = check_chain_init(&t, k, s, r, q_start, st, &run); e != HMC_OK || !run) return e;
   const bool replay = s->rng_mode == HMC_RNG_REPLAY;
-  if (replay && (!r || !r->p0)) return fail(HMC_EINVAL, "replay mode needs p0");
-  const int L_lo = s->L_high > s->L_low ? s->L_low : 5, L_hi = s->L_high > s->L_low ? s->L_high : 20;
-  const hmc::Layout lay = hmc::mix_layout(m->D, L_lo, L_hi);
+  const TrajRange L = init_traj_range(s);
+  const hmc::Layout lay = hmc::mix_layout(m->D, L.lo, L.hi);
   if (lay.K == 0) return fail(HMC_ENOTSUP, "D=%d too large for the mixture kernels", m->D);
   hmc::RandArgs a = rand_args(&t, k, s, replay ? r : nullptr, st, lay);
   a.qstart = q_start;
@@ -641,17 +685,9 @@ hmc_status hmc_mix_random_iters(const hmc_mixture* m, const hmc_kinetic* k, cons
   if (hmc_status e = check_mixture(m, k, "hmc_mix_random_iters")) return e;
   const hmc_target t = mix_shape(m);
   if (hmc_status e = check_schedule(&t, k, s, true)) return e;
-  if (!st) return fail(HMC_EINVAL, "null state");
-  if (hmc_status e = check_window(&t, s, st)) return e;
-  if (s->iter_begin < 1 || s->iter_end < s->iter_begin || s->iter_end > s->n_iter + 1)
-    return fail(HMC_EINVAL, "iteration range must satisfy 1 <= begin <= end <= Niter+1");
-  if (s->n_chains == 0) return HMC_OK;   // empty batch: zero-size buffers may be NULL
-  if (!st->q || !st->E_prev) return fail(HMC_EINVAL, "null state");
+  bool run;
+  if (hmc_status e = check_random_iters(&t, k, s, r, st, &run); e != HMC_OK || !run) return e;
   const bool replay = s->rng_mode == HMC_RNG_REPLAY;
-  if (replay && (!r || !r->p || !r->L || !r->lnu)) return fail(HMC_EINVAL, "replay mode needs p, L, lnu");
-  if (s->iter_end == s->iter_begin) return HMC_OK;
-  if (st->n_save > 0 && st->traj_q && st->traj_stride < s->L_high)
-    return fail(HMC_EINVAL, "traj_stride must be >= L_high");
   const hmc::Layout lay = hmc::mix_layout(m->D, s->L_low, s->L_high);
   if (lay.K == 0) return fail(HMC_ENOTSUP, "D=%d too large for the mixture kernels", m->D);
   const hmc::RandArgs a = rand_args(&t, k, s, replay ? r : nullptr, st, lay);
@@ -740,11 +776,9 @@ hmc_status glm_chain_init(const hmc_logistic* m, int family, const hmc_kinetic* 
   if (hmc_status e = check_logistic(m, k, what)) return e;
   const hmc_target t = logit_shape(m);
   if (hmc_status e = check_schedule(&t, k, s, false)) return e;
-  if (!st) return fail(HMC_EINVAL, "null state");
-  if (s->n_chains == 0) return HMC_OK;   // empty batch: zero-size buffers may be NULL
-  if (!st->q || !st->E_prev || !q_start) return fail(HMC_EINVAL, "null state/q_start");
+  bool run;
+  if (hmc_status e = check_chain_init(&t, k, s, r, q_start, st, &run); e != HMC_OK || !run) return e;
   const bool replay = s->rng_mode == HMC_RNG_REPLAY;
-  if (replay && (!r || !r->p0)) return fail(HMC_EINVAL, "replay mode needs p0");
   const hmc::Layout lay{0, 0, 0, (m->D + 1) / 2};
   hmc::RandArgs a = rand_args(&t, k, s, replay ? r : nullptr, st, lay);
   a.qstart = q_start;
@@ -769,17 +803,9 @@ hmc_status glm_random_iters(const hmc_logistic* m, int family, const hmc_kinetic
   if (hmc_status e = check_logistic(m, k, what)) return e;
   const hmc_target t = logit_shape(m);
   if (hmc_status e = check_schedule(&t, k, s, true)) return e;
-  if (!st) return fail(HMC_EINVAL, "null state");
-  if (hmc_status e = check_window(&t, s, st)) return e;
-  if (s->iter_begin < 1 || s->iter_end < s->iter_begin || s->iter_end > s->n_iter + 1)
-    return fail(HMC_EINVAL, "iteration range must satisfy 1 <= begin <= end <= Niter+1");
-  if (s->n_chains == 0) return HMC_OK;   // empty batch: zero-size buffers may be NULL
-  if (!st->q || !st->E_prev) return fail(HMC_EINVAL, "null state");
+  bool run;
+  if (hmc_status e = check_random_iters(&t, k, s, r, st, &run); e != HMC_OK || !run) return e;
   const bool replay = s->rng_mode == HMC_RNG_REPLAY;
-  if (replay && (!r || !r->p || !r->L || !r->lnu)) return fail(HMC_EINVAL, "replay mode needs p, L, lnu");
-  if (s->iter_end == s->iter_begin) return HMC_OK;
-  if (st->n_save > 0 && st->traj_q && st->traj_stride < s->L_high)
-    return fail(HMC_EINVAL, "traj_stride must be >= L_high");
   const hmc::Layout lay{0, 0, 0, (m->D + 1) / 2};
   const hmc::RandArgs a = rand_args(&t, k, s, replay ? r : nullptr, st, lay);
   return hip_status(hmc::launch_logit_iters(logit_args(m, a), family, replay, (hipStream_t)stream, ad), what);
@@ -889,8 +915,7 @@ hmc_status glm_nuts_iters(const hmc_glm* m, const hmc_kinetic* k, const hmc_sche
   if (hmc_status e = check_schedule(&t, k, s, false)) return e;
   if (!st) return fail(HMC_EINVAL, "null state");
   if (hmc_status e = check_window(&t, s, st)) return e;
-  if (s->iter_begin < 1 || s->iter_end < s->iter_begin || s->iter_end > s->n_iter + 1)
-    return fail(HMC_EINVAL, "iteration range must satisfy 1 <= begin <= end <= Niter+1");
+  if (hmc_status e = check_iter_range(s)) return e;
   if (s->d_max < 1 || s->d_max > hmc::kNutsDmaxMax)
     return fail(HMC_ENOTSUP, "%s: d_max=%d, the kernel takes 1 .. %d", what, s->d_max, hmc::kNutsDmaxMax);
   if (s->n_chains == 0) return HMC_OK;   // empty batch: zero-size buffers may be NULL
@@ -904,17 +929,7 @@ hmc_status glm_nuts_iters(const hmc_glm* m, const hmc_kinetic* k, const hmc_sche
                 "(hmc_glm_nuts_workspace_size)", what, (long long)workspace_bytes, d.D, (long long)s->n_chains,
                 s->d_max, (long long)need);
   if (s->iter_end == s->iter_begin) return HMC_OK;
-  const hmc::Layout lay{0, 0, 16, (d.D + 1) / 2};
-  hmc::RandArgs a = rand_args(&t, k, s, replay ? r : nullptr, st, lay);
-  a.d_max = s->d_max;
-  a.on_dmax = s->on_dmax;
-  a.ws = static_cast<double*>(workspace);
-  if (replay) {
-    a.tape = r->tape;
-    a.tape_stride = r->tape_stride;
-  }
-  a.traj_q = nullptr;   // the chain-0 capture is ignored (the reference never fills it for NUTS)
-  a.n_save = 0;
+  const hmc::RandArgs a = nuts_args(&t, k, s, r, st, d.D, workspace);
   return hip_status(hmc::launch_glm_nuts(logit_args(&d, a), m->family, replay, (hipStream_t)stream, ad), what);
 }
 

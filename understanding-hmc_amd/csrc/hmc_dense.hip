@@ -20,6 +20,7 @@
 #include "hmc_device.hpp"
 #include "hmc_internal.hpp"
 #include "hmc_dense_ops.hpp"
+#include "hmc_random_iter.hpp"
 
 // Waves per block (one block per CU: the LDS copy of P).  8 = two waves per SIMD at 256 registers:
 // the kernel spills ~88 B per lane, but one wave's MFMA gradient overlaps the other's RNG,
@@ -60,7 +61,7 @@ void k_dense_iters(DenseArgs a) {
 
   const int lane = threadIdx.x & (kWave - 1);
   const int h = lane >> 4;
-  unsigned long long n_acc = 0, n_acc_wu = 0, n_lf = 0, n_lf2 = 0, n_oob = 0;
+  RandomTally tally;
   // Persistent waves: P is staged into LDS once per block and the block's waves stride over the
   // 16-chain tiles.  With a.order (L-ordered tiles, one iteration per launch) tile t holds the
   // chains order[16t .. 16t+15], which share (up to bucket edges) one trajectory length, so no
@@ -173,8 +174,8 @@ void k_dense_iters(DenseArgs a) {
     energy_terms(maha, kin);
     const double E0 = 0.5 * (a.logc + chain_sum4(maha + kin));
     const bool post = it >= a.wu;
-    const bool write_row = post && ((it == a.niter) || ((it - a.wu + 1) % a.thin == 0));
-    const int64_t row = post ? (int64_t)((it - a.wu) / a.thin) : 0;
+    const bool write_row = stores_row(a, it);
+    const int64_t row = row_of(a, it);
     if (live && h == 0 && write_row) {
       if (a.Ec) a.Ec[c * (int64_t)a.Lc + row] = E0;
       if (a.dEc) a.dEc[c * (int64_t)a.Lc + row] = E0 - Eprev;
@@ -187,11 +188,9 @@ void k_dense_iters(DenseArgs a) {
       L = live ? a.rL[c * (int64_t)a.niter + (it - 1)] : 0;
       lnu = live ? a.rlnu[c * (int64_t)a.niter + (it - 1)] : 0.0;
     } else {
-      const uint4 r = draw_block(kDrawSlot, (uint32_t)it, gc, a.k0, a.k1);
-      L = live ? uniform_int(r.x, a.L_low, a.L_high) : 0;
-      const double u = u53(r.z, r.w);
-      lnu = u > 0.0 ? fast_log(u) : -__builtin_inf();   // log(random()), :461 (ocml log keeps its
-                                                        // constants in VGPRs across the loop)
+      const TrajDraw d = draw_traj(a, it, gc);          // (fast_log: ocml log keeps its constants in
+      L = live ? d.L : 0;                               // VGPRs across the loop)
+      lnu = d.lnu;
     }
     int Lmax = L;
 #pragma unroll
@@ -277,32 +276,11 @@ void k_dense_iters(DenseArgs a) {
       a.traj_len[it - 1] = (L > 0 ? L : 0) + 1;
       a.decision[it - 1] = accept ? 1 : 0;
     }
-    if (live && h == 0) {
-      if (accept) {
-        if (post) ++n_acc; else ++n_acc_wu;
-      } else if (it < a.i_oob) {
-        ++n_oob;
-      }
-      const unsigned long long Lp = L > 0 ? (unsigned long long)L : 0ull;
-      n_lf += Lp;
-      n_lf2 += Lp * Lp;
-    }
+    if (live && h == 0) tally.count(a, it, post, accept, L);
   }
   if (live && h == 0) a.Eprev[c] = Eprev;
   }   // tile loop
-  n_acc = wave_sum_u64(n_acc);
-  n_acc_wu = wave_sum_u64(n_acc_wu);
-  n_lf = wave_sum_u64(n_lf);
-  n_lf2 = wave_sum_u64(n_lf2);
-  n_oob = wave_sum_u64(n_oob);
-  if (lane == 0 && a.cnt) {
-    unsigned long long* cs = a.cnt + (wave_id & (HMC_COUNTER_SLOTS - 1)) * HMC_NCOUNTERS;
-    if (n_acc) atomicAdd(cs + HMC_CNT_ACCEPT, n_acc);
-    if (n_acc_wu) atomicAdd(cs + HMC_CNT_ACCEPT_WU, n_acc_wu);
-    if (n_lf) atomicAdd(cs + HMC_CNT_LEAPFROG, n_lf);
-    if (n_lf2) atomicAdd(cs + HMC_CNT_LEAPFROG_SQ, n_lf2);
-    if (n_oob) atomicAdd(cs + HMC_CNT_OOB_REJECT, n_oob);
-  }
+  tally.flush(a, lane, wave_id);
 }
 
 // p0 . inv(cov_p) . p0 of the initial momentum with a dense mass matrix (samplers.py:415-416):
@@ -380,9 +358,7 @@ __global__ __launch_bounds__(256) void k_dense_init(DenseArgs a, int MT) {
     a.q[c * a.D + d] = qs[d];
     if (a.qc && a.q_row0 == 0) a.qc[c * (int64_t)a.Lq * a.D + d] = qs[d];
   }
-  a.Eprev[c] = E0;
-  if (a.Ec) a.Ec[c * (int64_t)a.Lc] = E0;
-  if (a.dEc) a.dEc[c * (int64_t)a.Lc] = 0.0;
+  store_init_energy(a, c, E0);
 }
 
 // ---- L-ordered tiles (one iteration per launch): counting sort of the chains by this

@@ -41,6 +41,7 @@
 // One arithmetic for both fp_mode values (fast_exp / fast_log of hmc_device.hpp are ~1 ulp fp64,
 // not bit-identical to NumPy's).  Built with -ffp-contract=off; the FMAs are explicit.
 #include "hmc_glm_ops.hpp"
+#include "hmc_random_iter.hpp"
 
 namespace hmc {
 
@@ -65,11 +66,7 @@ __global__ __launch_bounds__(64 * kLogitWaves) void k_logit_init(LogitArgs x) {
   const double E0 = chain_sum4(vp + kinetic_part<MT>(t, sd, p));
   store_dims<MT>(a.q + t.c * (int64_t)a.D, t, q);
   if (a.qc && a.q_row0 == 0) store_dims<MT>(a.qc + t.c * (int64_t)a.Lq * a.D, t, q);
-  if (t.live && t.h == 0) {
-    a.Eprev[t.c] = E0;
-    if (a.Ec) a.Ec[t.c * (int64_t)a.Lc] = E0;
-    if (a.dEc) a.dEc[t.c * (int64_t)a.Lc] = 0.0;
-  }
+  if (t.live && t.h == 0) store_init_energy(a, t.c, E0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -101,7 +98,7 @@ void k_logit_iters(ItersKernelArgs<ADAPT> x) {
   load_dims<MT>(qrow, t, q);
   double Eprev = t.live ? a.Eprev[t.c] : 0.0;
   double* const qcb = a.qc ? a.qc + t.c * (int64_t)a.Lq * a.D : nullptr;
-  unsigned long long n_acc = 0, n_acc_wu = 0, n_lf = 0, n_lf2 = 0, n_oob = 0;
+  RandomTally tally;
   // chain-0 trajectory capture (samplers.py:442-452): the wave holding global chain 0 (lane 0)
   const bool cap_wave = a.traj_q && uniform_i((int)(__builtin_amdgcn_readfirstlane((int)(gc & 0xffffffff)) == 0 &&
                                                     __builtin_amdgcn_readfirstlane((int)(gc >> 32)) == 0));
@@ -119,8 +116,8 @@ void k_logit_iters(ItersKernelArgs<ADAPT> x) {
   for (int it = a.it0; it < a.it1; ++it) {
     draw_momentum<MT, REPLAY, true>(a, t, sd, it, gc, s_ntab, p);          // samplers.py:431
     const bool post = it >= a.wu;
-    const bool write_row = post && ((it == a.niter) || ((it - a.wu + 1) % a.thin == 0));
-    const int64_t row = post ? (int64_t)((it - a.wu) / a.thin) : 0;
+    const bool write_row = stores_row(a, it);
+    const int64_t row = row_of(a, it);
     // ---- trajectory length (:441) and log-uniform for the MH test (:461), per chain
     int L;
     double lnu;
@@ -128,10 +125,9 @@ void k_logit_iters(ItersKernelArgs<ADAPT> x) {
       L = t.live ? a.rL[t.c * (int64_t)a.niter + (it - 1)] : 0;
       lnu = t.live ? a.rlnu[t.c * (int64_t)a.niter + (it - 1)] : 0.0;
     } else {
-      const uint4 r = draw_block(kDrawSlot, (uint32_t)it, gc, a.k0, a.k1);
-      L = t.live ? uniform_int(r.x, a.L_low, a.L_high) : 0;
-      const double u = u53(r.z, r.w);
-      lnu = u > 0.0 ? fast_log(u) : -__builtin_inf();      // log(random()), :461
+      const TrajDraw d = draw_traj(a, it, gc);
+      L = t.live ? d.L : 0;
+      lnu = d.lnu;
     }
     const int Lmax = wave_max_i32(L);
     const bool cap = cap_wave && it <= a.n_save;
@@ -194,16 +190,7 @@ void k_logit_iters(ItersKernelArgs<ADAPT> x) {
       a.traj_len[it - 1] = (L > 0 ? L : 0) + 1;
       a.decision[it - 1] = accept ? 1 : 0;
     }
-    if (t.live && t.h == 0) {
-      if (accept) {
-        if (post) ++n_acc; else ++n_acc_wu;
-      } else if (it < a.i_oob) {
-        ++n_oob;                                           // reference would raise IndexError (Q5)
-      }
-      const unsigned long long Lp = L > 0 ? (unsigned long long)L : 0ull;   // xrange(1, L+1) is empty for L <= 0
-      n_lf += Lp;
-      n_lf2 += Lp * Lp;
-    }
+    if (t.live && t.h == 0) tally.count(a, it, post, accept, L);
   }
 
   // ---- state write-back and counters (a.q already holds q)
@@ -211,19 +198,7 @@ void k_logit_iters(ItersKernelArgs<ADAPT> x) {
     a.Eprev[t.c] = Eprev;
     if constexpr (ADAPT) adapt_store(ax.state + t.c * HMC_ADAPT_STRIDE, ad);
   }
-  n_acc = wave_sum_u64(n_acc);
-  n_acc_wu = wave_sum_u64(n_acc_wu);
-  n_lf = wave_sum_u64(n_lf);
-  n_lf2 = wave_sum_u64(n_lf2);
-  n_oob = wave_sum_u64(n_oob);
-  if (t.lane == 0 && a.cnt) {   // per-wave counts into one of HMC_COUNTER_SLOTS rows
-    unsigned long long* cs = a.cnt + (t.tile & (HMC_COUNTER_SLOTS - 1)) * HMC_NCOUNTERS;
-    if (n_acc) atomicAdd(cs + HMC_CNT_ACCEPT, n_acc);
-    if (n_acc_wu) atomicAdd(cs + HMC_CNT_ACCEPT_WU, n_acc_wu);
-    if (n_lf) atomicAdd(cs + HMC_CNT_LEAPFROG, n_lf);
-    if (n_lf2) atomicAdd(cs + HMC_CNT_LEAPFROG_SQ, n_lf2);
-    if (n_oob) atomicAdd(cs + HMC_CNT_OOB_REJECT, n_oob);
-  }
+  tally.flush(a, t.lane, t.tile);
 }
 
 // ------------------------------------------------------------------------------------------

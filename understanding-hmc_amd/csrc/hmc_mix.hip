@@ -3,10 +3,11 @@
 //
 // Replaces HMC_sampler.gen_sample_random (samplers.py:387-491) and leap_frog / E (:811-839) for
 //     V(q) = -log sum_k w_k N(q; mu_k, diag var_k).
-// The layout, the row bookkeeping (Q5, Q14, thinning), the Philox keying and the counters are those
-// of the lane-group kernel (hmc_random.hip): a chain's D coordinates live in lpc consecutive lanes
-// of a wave64, lane s owning pairs k = s + lpc*j (j < K); cpw chains share a wave; above 64 dims one
-// wave holds one chain (lpc = 64).  The state stays in registers across the fused iterations.
+// The layout and the Philox keying (hmc_lane_group.hpp), the row bookkeeping (Q5, Q14, thinning) and
+// the counters (hmc_random_iter.hpp) are those of the lane-group kernel (hmc_random.hip): a chain's D
+// coordinates live in lpc consecutive lanes of a wave64, lane s owning pairs k = s + lpc*j (j < K);
+// cpw chains share a wave; above 64 dims one wave holds one chain (lpc = 64).  The state stays in
+// registers across the fused iterations.
 //
 // One gradient evaluation at q (every per-chain scalar is a lane-group shuffle reduction, no LDS):
 //     m_k  = sum_d prec_kd (q_d - mu_kd)^2          two components' partial sums per shuffle tree
@@ -27,33 +28,15 @@
 // fast_log of hmc_device.hpp), which cannot be bit-identical to NumPy's, so there is no EXACT
 // instance.  Built with -ffp-contract=off; the FMAs are explicit.
 #include "hmc_device.hpp"
+#include "hmc_lane_group.hpp"
 #include "hmc_mix.hpp"
+#include "hmc_random_iter.hpp"
 
 namespace hmc {
 
 namespace {
 
 constexpr int kMixK = HMC_MIX_MAX_COMPONENTS;
-
-struct Lane {
-  int lane, g, s, base;
-  int64_t c;       // local chain (or row) index
-  bool active;     // lane belongs to a live chain
-  bool leader;     // first lane of a live chain's group
-};
-
-__device__ __forceinline__ Lane lane_info(const RandArgs& a) {
-  Lane L;
-  L.lane = threadIdx.x & (kWave - 1);
-  const int64_t wave = (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
-  L.g = L.lane / a.lpc;
-  L.s = L.lane - L.g * a.lpc;
-  L.base = L.g * a.lpc;
-  L.c = wave * a.cpw + L.g;
-  L.active = (L.g < a.cpw) && (L.c < a.n);
-  L.leader = L.active && (L.s == 0);
-  return L;
-}
 
 // Byte offsets, inside a [D] row, of a lane's coordinates 2k and 2k+1: 32-bit, computed once per
 // launch, so that every table load is a uniform row base plus a VGPR offset.  A padding slot (or a
@@ -245,62 +228,12 @@ __device__ __forceinline__ void kick(const double (&hk)[2 * K], const double (&g
   for (int e = 0; e < 2 * K; ++e) p[e] = __builtin_fma(-hk[e], g[e], p[e]);
 }
 
-template <int K, bool REPLAY>
-__device__ __forceinline__ void draw_momentum(const RandArgs& a, const Lane& ln, int it, const int (&kk)[K],
-                                              const bool (&pv)[K], double (&p)[2 * K]) {
-  const bool even = (a.D & 1) == 0;
-  const uint64_t gc = (uint64_t)(a.chain_offset + ln.c);
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    p[2 * j] = 0.0;
-    p[2 * j + 1] = 0.0;
-    if (pv[j]) {
-      const int d = 2 * kk[j];
-      if constexpr (REPLAY) {
-        const double* row = (it == 0) ? a.rp0 + ln.c * (int64_t)a.D
-                                      : a.rp + (ln.c * (int64_t)a.niter + (it - 1)) * a.D;
-        load_pair(row, kk[j], even, d + 1 < a.D, p[2 * j], p[2 * j + 1]);
-      } else {
-        normal_pair(draw_block((uint32_t)kk[j], (uint32_t)it, gc, a.k0, a.k1), p[2 * j], p[2 * j + 1]);
-        if (a.pscale) {
-          p[2 * j] *= a.pscale[d];
-          if (d + 1 < a.D) p[2 * j + 1] *= a.pscale[d + 1];
-        }
-      }
-      if (d + 1 >= a.D) p[2 * j + 1] = 0.0;
-    }
-  }
-}
-
 template <int K>
 __device__ __forceinline__ void slots(const RandArgs& a, const Lane& ln, int (&kk)[K], bool (&pv)[K],
                                       PairAt (&at_)[K]) {
+  lane_slots<K>(a, ln, kk, pv);
 #pragma unroll
-  for (int j = 0; j < K; ++j) {
-    kk[j] = ln.s + a.lpc * j;
-    pv[j] = ln.active && kk[j] < a.npairs;
-    at_[j] = pair_at(a.D, kk[j], pv[j]);
-  }
-}
-
-template <int K>
-__device__ __forceinline__ void load_row(const double* row, const RandArgs& a, const int (&kk)[K], const bool (&pv)[K],
-                                         double (&x)[2 * K]) {
-  const bool even = (a.D & 1) == 0;
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    x[2 * j] = x[2 * j + 1] = 0.0;
-    if (pv[j]) load_pair(row, kk[j], even, 2 * kk[j] + 1 < a.D, x[2 * j], x[2 * j + 1]);
-  }
-}
-
-template <int K>
-__device__ __forceinline__ void store_row(double* row, const RandArgs& a, const int (&kk)[K], const bool (&pv)[K],
-                                          const double (&x)[2 * K]) {
-  const bool even = (a.D & 1) == 0;
-#pragma unroll
-  for (int j = 0; j < K; ++j)
-    if (pv[j]) store_pair(row, kk[j], even, 2 * kk[j] + 1 < a.D, x[2 * j], x[2 * j + 1]);
+  for (int j = 0; j < K; ++j) at_[j] = pair_at(a.D, kk[j], pv[j]);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -315,15 +248,11 @@ __global__ __launch_bounds__(256) void k_mix_init(MixArgs m) {
   double q[2 * K], p[2 * K], g[2 * K];
   slots<K>(a, ln, kk, pv, at_);
   load_row<K>(a.qstart + ln.c * (int64_t)a.D, a, kk, pv, q);
-  draw_momentum<K, REPLAY>(a, ln, 0, kk, pv, p);
+  draw_momentum<K, true, REPLAY>(a, ln, 0, kk, pv, p);
   const double E0 = mix_grad<K>(m, ln, at_, q, g) + kinetic<K>(a, ln, kk, p);
   store_row<K>(a.q + ln.c * (int64_t)a.D, a, kk, pv, q);
   if (a.qc && a.q_row0 == 0) store_row<K>(a.qc + ln.c * (int64_t)a.Lq * a.D, a, kk, pv, q);
-  if (ln.leader) {
-    a.Eprev[ln.c] = E0;
-    if (a.Ec) a.Ec[ln.c * (int64_t)a.Lc] = E0;
-    if (a.dEc) a.dEc[ln.c * (int64_t)a.Lc] = 0.0;
-  }
+  if (ln.leader) store_init_energy(a, ln.c, E0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -341,19 +270,19 @@ __global__ __launch_bounds__(256) void k_mix_iters(MixArgs m) {
   step_consts<K>(a, kk, pv, dtc, hk);
   load_row<K>(a.q + ln.c * (int64_t)a.D, a, kk, pv, q);
   double Eprev = ln.active ? a.Eprev[ln.c] : 0.0;
-  unsigned long long n_acc = 0, n_acc_wu = 0, n_lf = 0, n_lf2 = 0, n_oob = 0;
+  RandomTally tally;
   int it_base = a.it0 - a.lpc, draw_L = 0;     // cached (L, log u) draws (Philox mode)
   double draw_lnu = 0.0;
 
   for (int it = a.it0; it < a.it1; ++it) {
     // ---- momentum resample (samplers.py:431) and initial energy (:434); the same pass gives the
     // gradient the first half kick needs
-    draw_momentum<K, REPLAY>(a, ln, it, kk, pv, p);
+    draw_momentum<K, true, REPLAY>(a, ln, it, kk, pv, p);
     double V = mix_grad<K>(m, ln, at_, q, g);
     const double E0 = V + kinetic<K>(a, ln, kk, p);
     const bool post = it >= a.wu;
-    const bool write_row = post && ((it == a.niter) || ((it - a.wu + 1) % a.thin == 0));
-    const int64_t row = post ? (int64_t)((it - a.wu) / a.thin) : 0;
+    const bool write_row = stores_row(a, it);
+    const int64_t row = row_of(a, it);
     if (ln.leader && write_row) {                        // :436-438 (Q14)
       if (a.Ec) __builtin_nontemporal_store(E0, a.Ec + ln.c * (int64_t)a.Lc + row);
       if (a.dEc) __builtin_nontemporal_store(E0 - Eprev, a.dEc + ln.c * (int64_t)a.Lc + row);
@@ -371,10 +300,9 @@ __global__ __launch_bounds__(256) void k_mix_iters(MixArgs m) {
       // iteration it reads them from lane base + (it - it_base)
       if (it - it_base >= a.lpc) {
         it_base = it;
-        const uint4 r = draw_block(kDrawSlot, (uint32_t)(it + ln.s), gc, a.k0, a.k1);
-        draw_L = uniform_int(r.x, a.L_low, a.L_high);
-        const double u = u53(r.z, r.w);
-        draw_lnu = u > 0.0 ? fast_log(u) : -__builtin_inf();   // log(random()), :461
+        const TrajDraw d = draw_traj(a, it + ln.s, gc);
+        draw_L = d.L;
+        draw_lnu = d.lnu;
       }
       L = __shfl(draw_L, ln.base + (it - it_base), kWave);
       lnu = __shfl(draw_lnu, ln.base + (it - it_base), kWave);
@@ -422,35 +350,13 @@ __global__ __launch_bounds__(256) void k_mix_iters(MixArgs m) {
       a.traj_len[it - 1] = (L > 0 ? L : 0) + 1;
       a.decision[it - 1] = accept ? 1 : 0;
     }
-    if (ln.leader) {
-      if (accept) {
-        if (post) ++n_acc; else ++n_acc_wu;
-      } else if (it < a.i_oob) {
-        ++n_oob;                                         // reference would raise IndexError (Q5)
-      }
-      const unsigned long long Lp = L > 0 ? (unsigned long long)L : 0ull;  // xrange(1, L+1) is empty for L <= 0
-      n_lf += Lp;
-      n_lf2 += Lp * Lp;
-    }
+    if (ln.leader) tally.count(a, it, post, accept, L);
   }
 
   // ---- state write-back and counters
   store_row<K>(a.q + ln.c * (int64_t)a.D, a, kk, pv, q);
   if (ln.leader) a.Eprev[ln.c] = Eprev;
-  n_acc = wave_sum_u64(n_acc);
-  n_acc_wu = wave_sum_u64(n_acc_wu);
-  n_lf = wave_sum_u64(n_lf);
-  n_lf2 = wave_sum_u64(n_lf2);
-  n_oob = wave_sum_u64(n_oob);
-  if (ln.lane == 0 && a.cnt) {   // per-wave counts into one of HMC_COUNTER_SLOTS rows
-    const int64_t wv = (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
-    unsigned long long* cs = a.cnt + (wv & (HMC_COUNTER_SLOTS - 1)) * HMC_NCOUNTERS;
-    if (n_acc) atomicAdd(cs + HMC_CNT_ACCEPT, n_acc);
-    if (n_acc_wu) atomicAdd(cs + HMC_CNT_ACCEPT_WU, n_acc_wu);
-    if (n_lf) atomicAdd(cs + HMC_CNT_LEAPFROG, n_lf);
-    if (n_lf2) atomicAdd(cs + HMC_CNT_LEAPFROG_SQ, n_lf2);
-    if (n_oob) atomicAdd(cs + HMC_CNT_OOB_REJECT, n_oob);
-  }
+  tally.flush(a, ln.lane, (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -479,11 +385,6 @@ __global__ __launch_bounds__(256) void k_mix_rows(MixArgs m) {
     const double E = V + kinetic<K>(a, ln, kk, p);
     if (ln.leader) m.row_E[ln.c] = E;
   }
-}
-
-dim3 grid_for(const RandArgs& a) {
-  const int64_t waves = (a.n + a.cpw - 1) / a.cpw;
-  return dim3((unsigned)((waves + 3) / 4));
 }
 
 template <int K>

@@ -13,6 +13,7 @@
 #ifdef __HIPCC__
 #include "hmc_device.hpp"
 #include "hmc_internal.hpp"
+#include "hmc_random_iter.hpp"   // stores_row: the row rule shared with the Random kernels
 #define HMC_TREE_FN __host__ __device__ __forceinline__
 #else
 #define HMC_TREE_FN inline
@@ -141,11 +142,6 @@ struct NutsDraws {
     return direction ? (double)(r.x & 1u) : u53(r.z, r.w);
   }
 };
-
-// whether iteration `it` stores a row of q_chain / E_chain / dE_chain (samplers.py:571-573, :786-791)
-__device__ __forceinline__ bool stores_row(const RandArgs& a, int it) {
-  return it >= a.wu && ((it == a.niter) || ((it - a.wu + 1) % a.thin == 0));
-}
 
 // row of the counter block that a kernel's slot index (wave, chain) adds to
 __device__ __forceinline__ unsigned long long* nuts_counter_row(unsigned long long* cnt, int64_t slot_index) {

@@ -20,6 +20,8 @@
 
 #include "hmc_device.hpp"
 #include "hmc_internal.hpp"
+#include "hmc_lane_group.hpp"
+#include "hmc_random_iter.hpp"
 #include "hmc_target_ops.hpp"
 
 namespace hmc {
@@ -28,26 +30,6 @@ namespace {
 
 __device__ __forceinline__ unsigned long long stamp(bool on) {
   return on ? __builtin_amdgcn_s_memtime() : 0ull;
-}
-
-struct Lane {
-  int lane, g, s, base;
-  int64_t c;       // local chain index
-  bool active;     // lane belongs to a live chain
-  bool leader;     // first lane of a live chain's group
-};
-
-__device__ __forceinline__ Lane lane_info(const RandArgs& a) {
-  Lane L;
-  L.lane = threadIdx.x & (kWave - 1);
-  const int64_t wave = (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
-  L.g = L.lane / a.lpc;
-  L.s = L.lane - L.g * a.lpc;
-  L.base = L.g * a.lpc;
-  L.c = wave * a.cpw + L.g;
-  L.active = (L.g < a.cpw) && (L.c < a.n);
-  L.leader = L.active && (L.s == 0);
-  return L;
 }
 
 template <int K, bool GEN>
@@ -69,64 +51,21 @@ __device__ __forceinline__ double chain_energy(const RandArgs& a, const Lane& ln
   return 0.5 * (a.logc + tot);
 }
 
-template <int K, bool GEN, bool REPLAY>
-__device__ __forceinline__ void draw_momentum(const RandArgs& a, const Lane& ln, int it, const int (&kk)[K],
-                                              const bool (&pv)[K], double (&p)[2 * K]) {
-  const bool even = (a.D & 1) == 0;
-  const uint64_t gc = (uint64_t)(a.chain_offset + ln.c);
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    p[2 * j] = 0.0;
-    p[2 * j + 1] = 0.0;
-    if (pv[j]) {
-      const int d = 2 * kk[j];
-      if constexpr (REPLAY) {
-        const double* row = (it == 0) ? a.rp0 + ln.c * (int64_t)a.D
-                                      : a.rp + (ln.c * (int64_t)a.niter + (it - 1)) * a.D;
-        load_pair(row, kk[j], even, d + 1 < a.D, p[2 * j], p[2 * j + 1]);
-      } else {
-        normal_pair(draw_block((uint32_t)kk[j], (uint32_t)it, gc, a.k0, a.k1), p[2 * j], p[2 * j + 1]);
-        if (GEN && a.pscale) {
-          p[2 * j] *= a.pscale[d];
-          if (d + 1 < a.D) p[2 * j + 1] *= a.pscale[d + 1];
-        }
-      }
-      if (d + 1 >= a.D) p[2 * j + 1] = 0.0;
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------
 // Chain initialisation (samplers.py:413-420): q_chain[:,0] = q_start, E_chain[:,0] = E(q, p0).
 template <int K, bool GEN, bool REPLAY>
 __global__ __launch_bounds__(256) void k_random_init(RandArgs a) {
   const Lane ln = lane_info(a);
-  const bool even = (a.D & 1) == 0;
   int kk[K];
   bool pv[K];
   double q[2 * K], p[2 * K];
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    kk[j] = ln.s + a.lpc * j;
-    pv[j] = ln.active && kk[j] < a.npairs;
-    q[2 * j] = q[2 * j + 1] = 0.0;
-    if (pv[j]) load_pair(a.qstart + ln.c * (int64_t)a.D, kk[j], even, 2 * kk[j] + 1 < a.D, q[2 * j], q[2 * j + 1]);
-  }
+  lane_slots<K>(a, ln, kk, pv);
+  load_row<K>(a.qstart + ln.c * (int64_t)a.D, a, kk, pv, q);
   draw_momentum<K, GEN, REPLAY>(a, ln, 0, kk, pv, p);
   const double E0 = chain_energy<K, GEN>(a, ln, kk, pv, q, p);
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    if (pv[j]) {
-      const bool v1 = 2 * kk[j] + 1 < a.D;
-      store_pair(a.q + ln.c * (int64_t)a.D, kk[j], even, v1, q[2 * j], q[2 * j + 1]);
-      if (a.qc && a.q_row0 == 0) store_pair(a.qc + ln.c * (int64_t)a.Lq * a.D, kk[j], even, v1, q[2 * j], q[2 * j + 1]);
-    }
-  }
-  if (ln.leader) {
-    a.Eprev[ln.c] = E0;
-    if (a.Ec) a.Ec[ln.c * (int64_t)a.Lc] = E0;
-    if (a.dEc) a.dEc[ln.c * (int64_t)a.Lc] = 0.0;
-  }
+  store_row<K>(a.q + ln.c * (int64_t)a.D, a, kk, pv, q);
+  if (a.qc && a.q_row0 == 0) store_row<K>(a.qc + ln.c * (int64_t)a.Lq * a.D, a, kk, pv, q);
+  if (ln.leader) store_init_energy(a, ln.c, E0);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -135,20 +74,14 @@ template <int K, bool EXACT, bool GEN, bool REPLAY>
 __global__ __launch_bounds__(256) void k_random_iters(RandArgs a) {
   const unsigned long long t_start = stamp(a.stamps != nullptr);
   const Lane ln = lane_info(a);
-  const bool even = (a.D & 1) == 0;
   const uint64_t gc = (uint64_t)(a.chain_offset + ln.c);
   int kk[K];
   bool pv[K];
   double q[2 * K], p[2 * K], qi[2 * K], t[2 * K];
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    kk[j] = ln.s + a.lpc * j;
-    pv[j] = ln.active && kk[j] < a.npairs;
-    q[2 * j] = q[2 * j + 1] = 0.0;
-    if (pv[j]) load_pair(a.q + ln.c * (int64_t)a.D, kk[j], even, 2 * kk[j] + 1 < a.D, q[2 * j], q[2 * j + 1]);
-  }
+  lane_slots<K>(a, ln, kk, pv);
+  load_row<K>(a.q + ln.c * (int64_t)a.D, a, kk, pv, q);
   double Eprev = ln.active ? a.Eprev[ln.c] : 0.0;
-  unsigned long long n_acc = 0, n_acc_wu = 0, n_lf = 0, n_lf2 = 0, n_oob = 0;
+  RandomTally tally;
   int it_base = a.it0 - a.lpc, draw_L = 0;     // cached (L, log u) draws (Philox mode)
   double draw_lnu = 0.0;
   unsigned long long ph[6] = {0, 0, 0, 0, 0, 0};   // diagnostic phase timers (stamps build path)
@@ -171,8 +104,8 @@ __global__ __launch_bounds__(256) void k_random_iters(RandArgs a) {
     const double E0 = (a.dbg & 2) ? 0.0 : chain_energy<K, GEN>(a, ln, kk, pv, q, p);
     unsigned long long t_2 = stamp(st_on);
     const bool post = it >= a.wu;
-    const bool write_row = post && ((it == a.niter) || ((it - a.wu + 1) % a.thin == 0));
-    const int64_t row = post ? (int64_t)((it - a.wu) / a.thin) : 0;
+    const bool write_row = stores_row(a, it);
+    const int64_t row = row_of(a, it);
     if (ln.leader && write_row && !(a.dbg & 8)) {       // :436-438 (Q14)
       __builtin_nontemporal_store(E0, a.Ec + ln.c * (int64_t)a.Lc + row);
       __builtin_nontemporal_store(E0 - Eprev, a.dEc + ln.c * (int64_t)a.Lc + row);
@@ -190,10 +123,9 @@ __global__ __launch_bounds__(256) void k_random_iters(RandArgs a) {
       // iteration it reads them from lane base + (it - it_base)
       if (it - it_base >= a.lpc) {
         it_base = it;
-        const uint4 r = draw_block(kDrawSlot, (uint32_t)(it + ln.s), gc, a.k0, a.k1);
-        draw_L = uniform_int(r.x, a.L_low, a.L_high);
-        const double u = u53(r.z, r.w);
-        draw_lnu = u > 0.0 ? fast_log(u) : -__builtin_inf();   // log(random()), :461
+        const TrajDraw d = draw_traj(a, it + ln.s, gc);
+        draw_L = d.L;
+        draw_lnu = d.lnu;
       }
       L = __shfl(draw_L, ln.base + (it - it_base), kWave);
       lnu = __shfl(draw_lnu, ln.base + (it - it_base), kWave);
@@ -278,26 +210,13 @@ __global__ __launch_bounds__(256) void k_random_iters(RandArgs a) {
 #pragma unroll
       for (int e = 0; e < 2 * K; ++e) q[e] = qi[e];
     }
-    if (write_row && a.qc && !(a.dbg & 8) && row >= a.q_row0) {
-      double* rowp = a.qc + (ln.c * (int64_t)a.Lq + row % a.Lq) * a.D;
-#pragma unroll
-      for (int j = 0; j < K; ++j)
-        if (pv[j]) store_pair(rowp, kk[j], even, 2 * kk[j] + 1 < a.D, q[2 * j], q[2 * j + 1]);
-    }
+    if (write_row && a.qc && !(a.dbg & 8) && row >= a.q_row0)
+      store_row<K>(a.qc + (ln.c * (int64_t)a.Lq + row % a.Lq) * a.D, a, kk, pv, q);
     if (cap) {
       a.traj_len[it - 1] = (L > 0 ? L : 0) + 1;
       a.decision[it - 1] = accept ? 1 : 0;
     }
-    if (ln.leader) {
-      if (accept) {
-        if (post) ++n_acc; else ++n_acc_wu;
-      } else if (it < a.i_oob) {
-        ++n_oob;                                         // reference would raise IndexError (Q5)
-      }
-      const unsigned long long Lp = L > 0 ? (unsigned long long)L : 0ull;  // xrange(1, L+1) is empty for L <= 0
-      n_lf += Lp;
-      n_lf2 += Lp * Lp;
-    }
+    if (ln.leader) tally.count(a, it, post, accept, L);
     if (st_on) {
       const unsigned long long t_6 = stamp(true);
       ph[0] += t_1 - t_0;   // momentum draw
@@ -310,9 +229,7 @@ __global__ __launch_bounds__(256) void k_random_iters(RandArgs a) {
   }
 
   // ---- state write-back and counters
-#pragma unroll
-  for (int j = 0; j < K; ++j)
-    if (pv[j]) store_pair(a.q + ln.c * (int64_t)a.D, kk[j], even, 2 * kk[j] + 1 < a.D, q[2 * j], q[2 * j + 1]);
+  store_row<K>(a.q + ln.c * (int64_t)a.D, a, kk, pv, q);
   if (ln.leader) a.Eprev[ln.c] = Eprev;
   if (a.stamps && ln.lane == 0) {
     const int64_t wv = (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
@@ -326,20 +243,7 @@ __global__ __launch_bounds__(256) void k_random_iters(RandArgs a) {
     a.stamps[wv * kStampWords + 5] = ((unsigned long long)hwid << 32) | ((unsigned long long)(xcc & 0xffff) << 16) |
                            (a.stamps[wv * kStampWords + 5] & 0xffffull);
   }
-  n_acc = wave_sum_u64(n_acc);
-  n_acc_wu = wave_sum_u64(n_acc_wu);
-  n_lf = wave_sum_u64(n_lf);
-  n_lf2 = wave_sum_u64(n_lf2);
-  n_oob = wave_sum_u64(n_oob);
-  if (ln.lane == 0 && a.cnt) {   // per-wave counts into one of HMC_COUNTER_SLOTS rows
-    const int64_t wv = (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
-    unsigned long long* cs = a.cnt + (wv & (HMC_COUNTER_SLOTS - 1)) * HMC_NCOUNTERS;
-    if (n_acc) atomicAdd(cs + HMC_CNT_ACCEPT, n_acc);
-    if (n_acc_wu) atomicAdd(cs + HMC_CNT_ACCEPT_WU, n_acc_wu);
-    if (n_lf) atomicAdd(cs + HMC_CNT_LEAPFROG, n_lf);
-    if (n_lf2) atomicAdd(cs + HMC_CNT_LEAPFROG_SQ, n_lf2);
-    if (n_oob) atomicAdd(cs + HMC_CNT_OOB_REJECT, n_oob);
-  }
+  tally.flush(a, ln.lane, (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave));
 }
 
 template <int K>
@@ -370,11 +274,6 @@ template <int K>
 hipError_t launch_iters_k(const RandArgs& a, bool exact, bool gen, bool replay, dim3 grid, hipStream_t s) {
   return exact ? launch_iters_k2<K, true>(a, gen, replay, grid, s)
                : launch_iters_k2<K, false>(a, gen, replay, grid, s);
-}
-
-dim3 grid_for(const RandArgs& a) {
-  const int64_t waves = (a.n + a.cpw - 1) / a.cpw;
-  return dim3((unsigned)((waves + 3) / 4));
 }
 
 }  // namespace
