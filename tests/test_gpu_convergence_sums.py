@@ -54,7 +54,7 @@ CASES = [
     (5, 117, 70, 0, 1, 1, 56),         # n = 58: two groups (a tail of 9 would exceed 8)
     (4, 240, 100, 0, 1, 1, 150),       # tmax beyond n - 1 = 119: the lags past it are 0
     # complete passes of 96 <= n <= 208 take the matrix cores (k_conv_mfma, Hankel tiles;
-    # hmc_diag.hip kMfmaMinN / kMfmaMaxN)
+    # hmc_diag.hpp kMfmaMinN, hmc_diag_mfma.hip kMfmaMaxN)
     (3, 193, 13, 0, 1, 1, 94),         # n = 96 (the smallest), D = 13: a partial dim group; 6 split
                                        # chains: one full chain group of 4 and a ragged one
     (3, 257, 13, 0, 1, 1, 126),        # n = 128, the same groups

@@ -1,4 +1,4 @@
-"""Host check of the matrix-core lag pass's tiling (csrc/hmc_diag.hip k_conv_mfma / k_mfma_dims):
+"""Host check of the matrix-core lag pass's tiling (csrc/hmc_diag_mfma.hip k_conv_mfma / k_mfma_dims):
 the loops of the kernel restated in NumPy, for every n the pass takes (96 .. 208).
 
 The kernel adds, for anchor step bi (b = 16 bi + 15), tile ti (T = 16 (ti - 1)) with

@@ -163,9 +163,9 @@ hipError_t launch_philox(uint4 c, uint32_t k0, uint32_t k1, int64_t n, uint32_t*
 hipError_t launch_rng_normals(uint32_t k0, uint32_t k1, int64_t chain0, int64_t n, int it, int npairs,
                               double* out, hipStream_t s);
 
-// Diagnostics (hmc_diag.hip).
+// Diagnostics (hmc_diag_sums.hip, hmc_diag_lags.hip, hmc_diag_mfma.hip, hmc_diag_stream.hip).
 int64_t diag_rowsum_work(int64_t rows, int D);
-// whether the lag kernel's 32-bit buffer offsets cover a strided view (hmc_diag.hip lag_view_ok)
+// whether the lag kernel's 32-bit buffer offsets cover a strided view (hmc_diag_lags.hip lag_view_ok)
 bool diag_view_ok(int64_t n_chains, int64_t cs, int64_t ss, int n, int D, int halves, int wrap, int slot0);
 int64_t diag_variogram_work(int64_t n_chains, int D, int nlags);
 int64_t diag_stream_groups(int64_t n_chains);

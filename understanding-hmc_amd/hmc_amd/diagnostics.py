@@ -125,7 +125,7 @@ def conv_tmax(n):
 
 
 def _fits(cs, ss, n, D):
-    """Whether the lag kernel's 32-bit buffer offsets cover a view (hmc_diag.hip lag_view_ok,
+    """Whether the lag kernel's 32-bit buffer offsets cover a view (hmc_diag_lags.hip lag_view_ok,
     pairs of halves): one chain's span must stay within 1 GiB."""
     if cs < n * ss:
         return False
@@ -286,39 +286,6 @@ def ess_vectorised(Vt, var, n, m, complete, truncate=False):
         n_eff = np.where(zero, float(m * n), m * n / (1 + 2 * ssum))
     n_eff[need] = np.nan
     return n_eff, need
-
-
-def _ess_dim(Vt, var, n, m, complete, truncate=False):
-    """The termination loop of utils.py:130-157 given V_1..V_T (Vt[t-1]); None if more lags
-    are needed (and not all lags are available yet).  truncate: the lags stop at len(Vt)
-    (streaming window), the sum ends there."""
-    def V(t):
-        return Vt[t - 1] if t - 1 < len(Vt) else None
-    v1, v2 = V(1), V(2)
-    if v1 is None or (v2 is None and not complete):
-        return None
-    with np.errstate(all="ignore"):
-        rho1 = 1. - v1 / (2 * var)
-        rho2 = 1. - v2 / (2 * var) if v2 is not None else np.nan
-    if (rho1 < 1e-2) or (rho1 < 1e-2):                                  # Q9 (sic)
-        sum_rho = 0
-    else:
-        rho = [rho1, rho2]
-        t = 1
-        while t < n - 2:
-            vt = V(t + 2)
-            if vt is None:
-                if truncate:
-                    break
-                return None
-            rho.append(1 - vt / (2 * var))
-            if ((t % 2) == 1) & ((rho[t] + rho[t + 1]) < 0):
-                break
-            t += 1
-        sum_rho = np.sum(rho[:t])
-        if sum_rho < 0:
-            sum_rho = 0
-    return m * n / (1 + 2 * sum_rho)
 
 
 def variogram(chains, var_num, t_lag):
