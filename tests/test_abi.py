@@ -137,6 +137,24 @@ def test_nuts_workspace_size_query(monkeypatch):
     assert L.hmc_nuts_workspace_size_ex(100, 1000, 10, 0, 1) == 0          # iters_per_call < 1
 
 
+def test_nuts_workspace_sizes_golden(monkeypatch):
+    """Every NUTS workspace size equals the one recorded in tests/golden/nuts_ws_sizes.json (written
+    by scripts/dev/gen_nuts_ws_sizes.py from the library as it was before the layouts moved into
+    csrc/hmc_nuts_layout.hpp): all four kernels' layouts, across the tile sizes of D, chain counts
+    around the 16-chain tiles and past the lockstep kernel's 1024-block cap, and the momenta
+    region's 32-iteration cap."""
+    import json
+    from hmc_amd import _lib as H
+    monkeypatch.setattr(H, "_lib", None)
+    L = H.lib()
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "nuts_ws_sizes.json")))
+    assert len(gold["nuts"]) == 16 * 7 * 3 * 3 * 2 and len(gold["glm"]) == 6 * 7 * 3
+    for D, n, d_max, iters, pm, nbytes in gold["nuts"]:
+        assert L.hmc_nuts_workspace_size_ex(D, n, d_max, iters, pm) == nbytes, (D, n, d_max, iters, pm)
+    for D, n, d_max, nbytes in gold["glm"]:
+        assert L.hmc_glm_nuts_workspace_size(D, n, d_max) == nbytes, (D, n, d_max)
+
+
 def test_nuts_sized_entry_refuses_small_workspace(monkeypatch):
     """hmc_nuts_iters_ws checks the workspace size on the host before anything runs (advisor r04: a
     workspace sized for fewer Philox momentum iterations, or none, was a silent device overrun):

@@ -31,9 +31,9 @@
 // tile-interleaved: element (tile, vec, m, lane) at ((tile nvec + vec) 4 MT + m) 64 + lane, so one
 // register's load or store is one contiguous 512-byte access of the wave (a chain-contiguous layout
 // would give 32-byte pieces).  nvec = 8 + 2 (d_max + 1): the two live points (their names swap on
-// acceptance), left q, p, g, right q, p, g, and d_max + 1 save slots of (q, p).  The tail holds one
-// replay-tape cursor per chain slot, zeroed by the caller before a run's first launch.
+// acceptance), left q, p, g, right q, p, g, and d_max + 1 save slots of (q, p).  (GlmNutsLayout)
 #include "hmc_glm_ops.hpp"
+#include "hmc_nuts_layout.hpp"
 #include "hmc_nuts_tree.hpp"
 
 namespace hmc {
@@ -47,8 +47,7 @@ enum : int { S_START = 0, S_INIT = 1, S_SUB = 2, S_TREE = 3, S_END = 4, S_DONE =
 
 // workspace vector ids of a chain: live points 0 and 1 (`old` names the old one), then the ends
 enum : int { V_LIVE = 0, V_LEFT = 2, V_RIGHT = 5, V_SLOTS = 8 };
-
-__host__ __device__ inline int glm_nuts_nvec(int d_max) { return V_SLOTS + 2 * (d_max + 1); }
+static_assert(V_SLOTS == GlmNutsLayout::kFixedVecs, "the save slots follow the layout's fixed vectors");
 
 // The wave's tile block, addressed through a wave-uniform buffer descriptor (SGPR base, 32-bit lane
 // offset, constant part of the offset in the instruction): no 64-bit address per (vector, m) is
@@ -130,11 +129,13 @@ void k_glm_nuts(NutsKernelArgs<ADAPT> x) {
   const TileLane t = tile_lane(a.n, a.D);
   if (t.tile >= a.ntiles) return;            // wave-uniform; no block barrier follows
   const uint64_t gc = (uint64_t)(a.chain_offset + t.c);
-  const int64_t tile_doubles = (int64_t)glm_nuts_nvec(a.d_max) * M * kWave;
+  const GlmNutsLayout L(a.n, MT, a.d_max);
   const int64_t tile = (int64_t)blockIdx.x * kLogitWaves + uniform_i(threadIdx.x / kWave);   // t.tile, in SGPRs
-  const TileWS w{__builtin_amdgcn_make_buffer_rsrc(a.ws + tile * tile_doubles, 0, (int)(tile_doubles * 8), 0x00020000),
+  const TileWS w{__builtin_amdgcn_make_buffer_rsrc(a.ws + L.slots(tile), 0, (int)(L.tile_doubles * 8), 0x00020000),
                  t.lane * 8};
-  int64_t* const tcur = reinterpret_cast<int64_t*>(a.ws + a.ntiles * tile_doubles) + t.tile * 16 + t.c16;
+  // L.cursors, through the tile count the launcher took from the same layout (launch_mt): dividing
+  // a.n again here costs the Bernoulli MT = 8 replay ADAPT instance 16 bytes of scratch per lane
+  int64_t* const tcur = reinterpret_cast<int64_t*>(a.ws + a.ntiles * L.tile_doubles) + t.tile * 16 + t.c16;
 
   double q[M], p[M];
   d4 g[MT];
@@ -344,7 +345,9 @@ void k_glm_nuts(NutsKernelArgs<ADAPT> x) {
 }
 
 template <int FAMILY, int MT>
-hipError_t launch_mt(const LogitArgs& x, bool replay, const hmc_adapt* ad, hipStream_t s) {
+hipError_t launch_mt(const LogitArgs& x0, bool replay, const hmc_adapt* ad, hipStream_t s) {
+  LogitArgs x = x0;
+  x.a.ntiles = GlmNutsLayout(x.a.n, MT, x.a.d_max).tiles;
   const dim3 grid((unsigned)((x.a.ntiles + kLogitWaves - 1) / kLogitWaves)), block(64 * kLogitWaves);
   if (ad) {
     const LogitAdaptArgs xa{x, *ad};
@@ -380,14 +383,11 @@ hipError_t launch_family(const LogitArgs& x, bool replay, const hmc_adapt* ad, h
 int64_t glm_nuts_ws_doubles(int64_t n, int D, int d_max) {
   const int MT = glm_tiles(D);
   if (!MT || n < 0 || d_max < 1 || d_max > kNutsDmaxMax) return 0;
-  const int64_t tiles = (n + 15) / 16;
-  return tiles * glm_nuts_nvec(d_max) * (4 * MT) * kWave + tiles * 16;   // vectors, then the tape cursors
+  return GlmNutsLayout(n, MT, d_max).total;
 }
 
-hipError_t launch_glm_nuts(const LogitArgs& x0, int family, bool replay, hipStream_t s, const hmc_adapt* ad) {
-  LogitArgs x = x0;
+hipError_t launch_glm_nuts(const LogitArgs& x, int family, bool replay, hipStream_t s, const hmc_adapt* ad) {
   if (x.a.n == 0 || x.a.it1 <= x.a.it0) return hipSuccess;
-  x.a.ntiles = (x.a.n + 15) / 16;
   switch (family) {
     case HMC_GLM_BERNOULLI: return launch_family<HMC_GLM_BERNOULLI>(x, replay, ad, s);
     case HMC_GLM_POISSON: return launch_family<HMC_GLM_POISSON>(x, replay, ad, s);

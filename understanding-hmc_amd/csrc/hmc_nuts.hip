@@ -14,14 +14,14 @@
 // new point; chains between trees (iteration end / start, sub-tree start) do their transition
 // work first.  A launch ends when every chain of the wave finished its iterations.
 // Per-chain vectors that trees keep (live points, both boundaries, the d_max+1 save slots) live
-// in a workspace in HBM (`ws`, hmc_nuts_workspace_size), chain-contiguous and zero padded so
-// lanes never branch on the dimension and chains that sit out a branch move no bytes.  The tail of the workspace holds the per-chain replay-tape cursors (zeroed by the
-// host before the first launch of a run).  All cross-lane reductions run in converged control flow.
+// in a workspace in HBM (`ws`; hmc_nuts_layout.hpp says what is where), zero padded so lanes never
+// branch on the dimension.  All cross-lane reductions run in converged control flow.
 #include <algorithm>
 
 #include "hmc_dense_ops.hpp"
 #include "hmc_device.hpp"
 #include "hmc_internal.hpp"
+#include "hmc_nuts_layout.hpp"
 #include "hmc_nuts_tree.hpp"
 
 namespace hmc {
@@ -31,27 +31,17 @@ namespace {
 // Waves per block (one block per CU: the LDS copy of P), one per SIMD with the whole register file.
 // 8 (two waves per SIMD, 256 registers each) was measured at 0.42x: the step spills ~560 B per lane
 // to scratch and the queue's tail grows (lane utilisation 0.80 -> 0.66).
-#ifndef HMC_NUTS_WAVES
-#define HMC_NUTS_WAVES 4
-#endif
-constexpr int kNutsWaves = HMC_NUTS_WAVES;
+constexpr int kNutsWaves = 4;
 
 // Chain affinity (work queue below): a launch's first K - kNutsTail iterations of every chain run in
 // units of kNutsBlock consecutive iterations (a slot keeps its chain from tree to tree inside a unit:
 // no write-back, drain, publish, poll or state loads between them), queued block-major so a chain's
 // next block waits behind the whole grid's current one; its last kNutsTail iterations run as one unit
-// per (chain, iteration), which keeps the launch's tail at one tree per slot.  kNutsBlock 1 gives the
-// per-tree units only.
+// per (chain, iteration), which keeps the launch's tail at one tree per slot.
 // (round 6, with the release/acquire hand-off: blocks of 12 beat 8 by 1.0%, 10 and 14 lost 0.3% and
 // 3%, 16 lost 2.5%: profiles/r06s_nuts_block_ab.txt)
-#ifndef HMC_NUTS_BLOCK
-#define HMC_NUTS_BLOCK 12
-#endif
-#ifndef HMC_NUTS_TAIL
-#define HMC_NUTS_TAIL 4
-#endif
-constexpr int kNutsBlock = HMC_NUTS_BLOCK;
-constexpr int kNutsTail = HMC_NUTS_TAIL;
+constexpr int kNutsBlock = 12;
+constexpr int kNutsTail = 4;
 
 // S_FETCH: the chain slot hands its chain back and takes the next (chain, iteration) unit of the
 // launch from the queue (or retires); S_WAIT: the unit's chain is still finishing its previous
@@ -68,9 +58,9 @@ enum : int { S_ITER_START = 0, S_READY = 2, S_ITER_END = 3, S_DONE = 4, S_FETCH 
 // taking slot polls that word with relaxed loads and, in the step a poll succeeds, issues one
 // agent-scope ACQUIRE fence before its (sc1) state loads: fence-fence synchronisation, so the
 // hand-off holds on any memory system the model covers, not only on today's gfx950 caches.  With
-// chain affinity (hand-offs once per kNutsBlock trees) it costs 2.5% against the relaxed sc1 +
-// vmcnt protocol alone (1.934e9 vs 1.982e9 lf/s, same box; -5 to -6% with a hand-off per tree);
-// that protocol stays as the dev A/B variant HMC_NUTS_RELAXED.
+// chain affinity (hand-offs once per kNutsBlock trees) it measured 2.5% slower than publishing and
+// polling with the relaxed sc1 + vmcnt protocol alone (1.934e9 vs 1.982e9 lf/s, same box; -5 to
+// -6% with a hand-off per tree); that protocol was rejected as less portable and is no longer built.
 // Reserving the next unit at tree start and polling its chain during the tree (so that a tree's
 // end costs one round trip) measured 1.77e9 -> 1.52e9 lf/s: those loads sit in the in-order vmcnt
 // queue ahead of the U-turn checks' loads, which then wait for them.
@@ -110,8 +100,7 @@ inline uint64_t nuts_wait_cap(int64_t slots, int64_t n, int d_max, int kb) {
 // point swaps the names instead of copying a vector.
 enum : int { V_OLD_Q = 0, V_OLD_G = 1, V_NEW_Q = 2, V_NEW_G = 3, V_LEFT_Q = 4, V_LEFT_P = 5, V_LEFT_G = 6,
              V_RIGHT_Q = 7, V_RIGHT_P = 8, V_RIGHT_G = 9, V_SLOTS = 10 };
-
-__device__ __forceinline__ int nuts_nvec(int d_max) { return V_SLOTS + 2 * (d_max + 1); }
+static_assert(V_SLOTS == NutsTreeLayout::kFixedVecs, "the save slots follow the layout's fixed vectors");
 
 // Phase timers of the debug build (make debug; HMC_DEBUG_STAMPS): wave-uniform s_memtime deltas per
 // part of a wave step, summed over the launch: 0 transitions, 1 half kick + drift, 2 gradient
@@ -119,46 +108,22 @@ __device__ __forceinline__ int nuts_nvec(int d_max) { return V_SLOTS + 2 * (d_ma
 // 6 progressive sampling, 7 sub-tree end; inside 0: 8 tree end (live point, row), 9 write-back +
 // drain + publish, 10 queue reservation, 11 poll + state loads, 12 momentum + tree start; 13 counts
 // the wave steps with a tree end.  The release library compiles none of it.
+// NUTS_TIMER(t, i) adds the time since timer t (t_ph: the parts of a step, t_sub: inside part 0) to
+// ph[i] and restarts it.
 #ifdef HMC_DEBUG_HOOKS
-#define NUTS_PHASE(i)                                        \
-  do {                                                       \
+#define NUTS_TIMER(t, i)                                        \
+  do {                                                          \
     const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-    ph[i] += t_ - t_ph;                                      \
-    t_ph = t_;                                               \
+    ph[i] += t_ - t;                                            \
+    t = t_;                                                     \
   } while (0)
 #else
-#define NUTS_PHASE(i) \
-  do {                \
-  } while (0)
-#endif
-#ifdef HMC_DEBUG_HOOKS
-#define NUTS_SUBPHASE(i)                                     \
-  do {                                                       \
-    const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-    ph[i] += t_ - t_sub;                                     \
-    t_sub = t_;                                              \
-  } while (0)
-#else
-#define NUTS_SUBPHASE(i) \
+#define NUTS_TIMER(t, i) \
   do {                   \
   } while (0)
 #endif
 
-// bytes of the work queue block, zeroed before every launch: head, a spare word, done[n] (u32),
-// padded to a multiple of 16
-__host__ __device__ inline size_t nuts_queue_bytes(int64_t n) { return (size_t)((16 + 4 * n + 15) / 16 * 16); }
-
-// Philox momenta are drawn ahead of the tree kernel (k_nuts_momenta) for up to kNutsMomIters
-// iterations per launch into the workspace tail: a tree start then costs a 16-byte load per lane
-// pair, issued with the chain's state loads, instead of ~23k clocks of Philox + Box-Muller that
-// the whole wave waited for at every tree end (profiles/r03_c5_nuts_phases.json), and the tree
-// kernel needs no Box-Muller tables in LDS.  Longer ranges run as several launches.
-constexpr int kNutsMomIters = 32;
-__host__ __device__ inline int64_t nuts_mom_doubles(int64_t n, int MT, int iters) {
-  return n * (iters < kNutsMomIters ? iters : kNutsMomIters) * 4 * MT * 4;
-}
-
-// Workspace: per chain slot, nvec vectors of Dp = 4M doubles (dims, zero padded), slot-contiguous,
+// Workspace (NutsTreeLayout::slots): per chain slot, nvec vectors of Dp = 4M doubles (dims, zero padded), slot-contiguous,
 // the 16 slots of a wave in one block addressed through a wave-uniform buffer descriptor (SGPR
 // base, 32-bit lane offset: no 64-bit addresses kept live).  Inside a vector, lane (c, h) keeps
 // its dims h + 4m in pairs (m, m+1) at byte (m/2)*64 + h*16: one chain's part of an access is
@@ -196,23 +161,6 @@ __device__ __forceinline__ void vstore_sg(const WaveWS& w, int v, int vl, const 
     const u32x2 lo = __builtin_bit_cast(u32x2, x[m] * sg), hi = __builtin_bit_cast(u32x2, x[m + 1] * sg);
     __builtin_amdgcn_raw_buffer_store_b128(u32x4{lo.x, lo.y, hi.x, hi.y}, w.r, vo, v * (4 * M * 8) + ws_elem(m), 0);
   }
-}
-
-template <int M>
-__device__ __forceinline__ void vput(const WaveWS& w, int v, int m, double x) {
-  __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, x), w.r, w.lane_off, v * (4 * M * 8) + ws_elem(m), 0);
-}
-
-template <int M>
-__device__ __forceinline__ double vget(const WaveWS& w, int v, int vl, int m) {
-  return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(w.r, w.lane_off + vl * (4 * M * 8),
-                                                                         v * (4 * M * 8) + ws_elem(m), 0));
-}
-
-template <int M>
-__device__ __forceinline__ void vput2(const WaveWS& w, int v, int m, double x0, double x1) {
-  const u32x2 lo = __builtin_bit_cast(u32x2, x0), hi = __builtin_bit_cast(u32x2, x1);
-  __builtin_amdgcn_raw_buffer_store_b128(u32x4{lo.x, lo.y, hi.x, hi.y}, w.r, w.lane_off, v * (4 * M * 8) + ws_elem(m), 0);
 }
 
 // dims m and m+1 (m even) in one 16-byte access
@@ -259,11 +207,24 @@ __device__ __forceinline__ double mac(double acc, double x, double y) {
 // Momenta of iterations [it0, it1) (K = it1 - it0 <= kNutsMomIters) for every chain: p ~ N(0, cov_p)
 // with a diagonal cov_p (samplers.py:565, :829), exactly the tree kernel's former in-kernel draws
 // (pair slot h + 4m -> dims h + 4m and h + 4m + 4, table Box-Muller, pscale, zero padding).
-// Layout: per (chain, iteration) one 4M-double vector, chain-major (c * K + it - it0; the buffer holds
-// min(kNutsMomIters, iterations per call) iterations, hmc_nuts_workspace_size_ex), in the
-// workspace's pair layout (ws_elem):
+// Into NutsTreeLayout's momenta region, each vector in the workspace's pair layout (ws_elem):
 // 16-byte slot s = 4j + h holds dims (h + 8j, h + 8j + 4), so slot s sits at doubles 2s..2s+1 and
 // consecutive threads write consecutive 16-byte slots.
+// The Philox momentum of pair slot d0 = h + 4m (dims d0 and d0 + 4) of iteration it of global chain
+// gc: table Box-Muller pair, scaled by pscale (diagonal cov_p), zero past D.
+template <bool GEN>
+__device__ __forceinline__ void momentum_pair(const RandArgs& a, const double* ntab, int d0, int it, uint64_t gc,
+                                              double& z0, double& z1) {
+  normal_pair_tab(draw_block((uint32_t)d0, (uint32_t)it, gc, a.k0, a.k1), ntab, z0, z1);
+  const int d1 = d0 + 4;
+  if (GEN && a.pscale) {
+    z0 *= a.pscale[min(d0, a.D - 1)];
+    z1 *= a.pscale[min(d1, a.D - 1)];
+  }
+  z0 = d0 < a.D ? z0 : 0.0;
+  z1 = d1 < a.D ? z1 : 0.0;
+}
+
 template <int MT, bool GEN>
 __global__ __launch_bounds__(256) void k_nuts_momenta(RandArgs a, double* __restrict__ pm) {
   constexpr int M = 4 * MT;
@@ -279,16 +240,19 @@ __global__ __launch_bounds__(256) void k_nuts_momenta(RandArgs a, double* __rest
     const int it = a.it0 + (int)(vec - c * K);
     const int h = r & 3, m = 2 * (r >> 2);
     double z0, z1;
-    normal_pair_tab(draw_block((uint32_t)(h + 4 * m), (uint32_t)it, (uint64_t)(a.chain_offset + c), a.k0, a.k1),
-                    s_ntab, z0, z1);
-    const int d0 = h + 4 * m, d1 = d0 + 4;
-    if (GEN && a.pscale) {
-      z0 *= a.pscale[min(d0, a.D - 1)];
-      z1 *= a.pscale[min(d1, a.D - 1)];
-    }
-    z0 = d0 < a.D ? z0 : 0.0;
-    z1 = d1 < a.D ? z1 : 0.0;
-    *reinterpret_cast<double2*>(pm + (c * K + (vec - c * K)) * (4 * M) + 2 * r) = make_double2(z0, z1);
+    momentum_pair<GEN>(a, s_ntab, h + 4 * m, it, (uint64_t)(a.chain_offset + c), z0, z1);
+    *reinterpret_cast<double2*>(pm + NutsTreeLayout::mom_vec(c, K, vec - c * K, MT) + 2 * r) = make_double2(z0, z1);
+  }
+}
+
+// A (chain, iteration) momentum of k_nuts_momenta, vector pv, into the lane's p (dims h + 4m)
+template <int M, int ME>
+__device__ __forceinline__ void load_momentum(const double* pv, int h, double (&p)[M]) {
+#pragma unroll
+  for (int m = 0; m < ME; m += 2) {
+    const double2 z = *reinterpret_cast<const double2*>(pv + 2 * h + 4 * m);
+    p[m] = z.x;
+    p[m + 1] = z.y;
   }
 }
 
@@ -322,14 +286,17 @@ void k_nuts_iters(RandArgs a) {
   // Draws are keyed by (chain, iteration), so results do not depend on which slot or wave runs a
   // tree.  The tree vectors are per slot (W), the tape cursors and hand-off words per chain.
   const int64_t wv = (int64_t)blockIdx.x * kNutsWaves + __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
-  const int64_t wave_doubles = (int64_t)nuts_nvec(a.d_max) * M * kWave;
-  const int64_t n_waves = (a.n + 15) / 16;
-  const WaveWS W{__builtin_amdgcn_make_buffer_rsrc(a.ws + wv * wave_doubles, 0, (int)(wave_doubles * 8), 0x00020000),
-                 (lane & 15) * nuts_nvec(a.d_max) * (4 * M * 8) + h * 16};
-  int64_t* const tcur = reinterpret_cast<int64_t*>(a.ws + n_waves * wave_doubles);
-  unsigned long long* const queue = reinterpret_cast<unsigned long long*>(tcur + n_waves * 16);   // zeroed per launch
-  unsigned* const done = reinterpret_cast<unsigned*>(queue + 2);    // per chain: iterations done (zeroed per launch)
-  const double* const pm = reinterpret_cast<const double*>(queue) + nuts_queue_bytes(a.n) / 8;   // k_nuts_momenta
+  const NutsTreeLayout L{a.n, MT, a.d_max, 0};
+  const int64_t wave_doubles = L.wave_doubles(), n_waves = L.n_waves();
+  const WaveWS W{__builtin_amdgcn_make_buffer_rsrc(a.ws + L.slots(wv), 0, (int)(wave_doubles * 8), 0x00020000),
+                 (lane & 15) * L.nvec() * (4 * M * 8) + h * 16};
+  // The two sizes first, then each region's pointer from the one before it by the layout's region
+  // sizes.  a.ws + L.queue() and a.ws + L.momenta() are the same addresses, but derived that way the
+  // c5 instance's prologue is shorter, its step loop sits elsewhere and it ran 0.45 % slower.
+  int64_t* const tcur = reinterpret_cast<int64_t*>(a.ws + L.cursors());
+  unsigned long long* const queue = reinterpret_cast<unsigned long long*>(tcur + L.n_cursors());   // zeroed per launch
+  unsigned* const done = reinterpret_cast<unsigned*>(queue + NutsTreeLayout::kQueueHead);   // per chain: iterations done
+  const double* const pm = reinterpret_cast<const double*>(queue) + L.queue_bytes() / 8;      // k_nuts_momenta
   const int n_blk = (a.nuts_kb + kNutsBlock - 1) / kNutsBlock;   // block units per chain
   const unsigned long long nb = (unsigned long long)a.n * (unsigned long long)n_blk;
   const unsigned long long n_units = nb + (unsigned long long)a.n * (unsigned long long)(a.it1 - a.it0 - a.nuts_kb);
@@ -388,21 +355,14 @@ void k_nuts_iters(RandArgs a) {
         Eprev = E_init;
         if (it < it_last) {                             // a block unit: the same chain's next tree,
           ++it;                                         // no hand-off (q, E_prev and the tape cursor
-          if constexpr (PG) {                           // stay in registers), its momentum loaded
-            const double* pv = pm + (c * (a.it1 - a.it0) + (it - a.it0)) * (4 * M) + 2 * h;
-#pragma unroll
-            for (int m = 0; m < ME; m += 2) {
-              const double2 z = *reinterpret_cast<const double2*>(pv + 4 * m);
-              p[m] = z.x;
-              p[m + 1] = z.y;
-            }
-          }
+          if constexpr (PG)                             // stay in registers), its momentum loaded
+            load_momentum<M, ME>(pm + NutsTreeLayout::mom_vec(c, a.it1 - a.it0, it - a.it0, MT), h, p);
           state = S_GRAD;                               // gradient at q in the next wave step
         } else {
           state = S_FETCH;                              // hand the chain back after its unit
         }
       }
-      NUTS_SUBPHASE(8);
+      NUTS_TIMER(t_sub, 8);
       if (state == S_FETCH && live) {                   // tree done: write the chain's state through
 #pragma unroll
         for (int m = 0; m < ME; ++m) {
@@ -414,18 +374,14 @@ void k_nuts_iters(RandArgs a) {
       }
       if (__builtin_amdgcn_ballot_w64(state == S_FETCH && live)) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the state has reached L2/memory ...
-#ifndef HMC_NUTS_RELAXED
         // one agent-scope release fence per wave step that publishes (an L2 write-back across
         // XCDs), then relaxed atomic publishes
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         if (state == S_FETCH && live && h == 0)
           __hip_atomic_store(done + c, (unsigned)(it + 1 - a.it0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-        if (state == S_FETCH && live && h == 0) st_wt(done + c, (unsigned)(it + 1 - a.it0));   // ... then publish
-#endif
         if (state == S_FETCH) live = false;
       }
-      NUTS_SUBPHASE(9);
+      NUTS_TIMER(t_sub, 9);
       if (__builtin_amdgcn_ballot_w64(state == S_FETCH)) {   // next unit from the queue (converged shuffle;
         const bool fetching = state == S_FETCH;              // skipped in the steps where no slot fetches)
         unsigned long long u = (fetching && h == 0) ? atomicAdd(queue, 1ull) : 0ull;
@@ -454,19 +410,14 @@ void k_nuts_iters(RandArgs a) {
           }
         }
       }
-      NUTS_SUBPHASE(10);
+      NUTS_TIMER(t_sub, 10);
       if (state == S_WAIT) {                            // the chain's previous iteration published?
         const unsigned need = (unsigned)(it - a.it0);
         bool ready = need == 0;
         if (!ready) {
-#ifndef HMC_NUTS_RELAXED
           // relaxed polls; the acquire fence (an L1 invalidate) once, in the step a poll succeeds
           ready = __hip_atomic_load(done + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= need;
           if (__builtin_amdgcn_ballot_w64(ready)) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#else
-          ready = ld_wt(done + c) >= need;
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // keep the state loads below the poll
-#endif
           if (!ready && ++waited > a.wait_cap) {   // broken hand-off: flag it and retire the slot
             ++n_giveup;
             state = S_DONE;
@@ -481,19 +432,12 @@ void k_nuts_iters(RandArgs a) {
           }
           Eprev = ld_wt_d(a.Eprev + c);
           tpos = REPLAY ? ld_wt(tcur + c) : 0;
-          if constexpr (PG) {                           // this iteration's momentum, with the state
-            const double* pv = pm + (c * (a.it1 - a.it0) + (it - a.it0)) * (4 * M) + 2 * h;
-#pragma unroll
-            for (int m = 0; m < ME; m += 2) {
-              const double2 z = *reinterpret_cast<const double2*>(pv + 4 * m);
-              p[m] = z.x;
-              p[m + 1] = z.y;
-            }
-          }
+          if constexpr (PG)                             // this iteration's momentum, with the state
+            load_momentum<M, ME>(pm + NutsTreeLayout::mom_vec(c, a.it1 - a.it0, it - a.it0, MT), h, p);
           state = S_GRAD;                               // gradient at q in the next wave step
         }
       }
-      NUTS_SUBPHASE(11);
+      NUTS_TIMER(t_sub, 11);
       const bool starting = state == S_ITER_START;
       double kin = 0.0;
       if (starting) {   // momentum (:565), dims h+4m, streamed to the boundaries: right = p, left = -p (:581-584)
@@ -516,15 +460,9 @@ void k_nuts_iters(RandArgs a) {
         } else {
 #pragma unroll
           for (int m = 0; m < ME; m += 2) {
-            double z0, z1;
-            normal_pair_tab(draw_block((uint32_t)(h + 4 * m), (uint32_t)it, gc, a.k0, a.k1), s_ntab, z0, z1);
             const int d0 = h + 4 * m, d1 = d0 + 4;
-            if (GEN && a.pscale) {
-              z0 *= a.pscale[min(d0, a.D - 1)];
-              z1 *= a.pscale[min(d1, a.D - 1)];
-            }
-            z0 = d0 < a.D ? z0 : 0.0;
-            z1 = d1 < a.D ? z1 : 0.0;
+            double z0, z1;
+            momentum_pair<GEN>(a, s_ntab, d0, it, gc, z0, z1);
             p[m] = z0;
             p[m + 1] = z1;
             if constexpr (!MASS) {
@@ -588,10 +526,10 @@ void k_nuts_iters(RandArgs a) {
         k = 0;
         state = S_READY;
       }
-      NUTS_SUBPHASE(12);
+      NUTS_TIMER(t_sub, 12);
     }
     if (!__builtin_amdgcn_ballot_w64(state != S_DONE)) break;
-    NUTS_PHASE(0);
+    NUTS_TIMER(t_ph, 0);
 
     // ================= one leapfrog for every chain inside a sub-tree (:612-614, :639)
     // chains outside a sub-tree are frozen by the EXEC mask of a divergent block (no per-dim
@@ -630,9 +568,9 @@ void k_nuts_iters(RandArgs a) {
         if ((m & 3) == 3) __builtin_amdgcn_sched_barrier(0);
       }
     }
-    NUTS_PHASE(1);
+    NUTS_TIMER(t_ph, 1);
     gradient<MT, GEN, true, SHORT>(a, sP, lane, h, q, acc);
-    NUTS_PHASE(2);
+    NUTS_TIMER(t_ph, 2);
     if (act) {
 #pragma unroll
       for (int m = 0; m < ME; ++m) {
@@ -685,7 +623,7 @@ void k_nuts_iters(RandArgs a) {
     }
     if (act && h == 0) ++n_lf;
     ++n_steps;
-    NUTS_PHASE(3);
+    NUTS_TIMER(t_ph, 3);
 
     // ================= process the new point
     bool reject = false, sub_end = false;
@@ -710,7 +648,7 @@ void k_nuts_iters(RandArgs a) {
         vstore<M, ME>(W, V_SLOTS + 1, 2 * s, p);
       }
     }
-    NUTS_PHASE(4);
+    NUTS_TIMER(t_ph, 4);
     // even point: sub-tree U-turn checks against check_points(mpt) (:699-736), converged loop
     const bool checking = later && !reject && (mpt & 1) == 0;
     {                                                   // the check against point mpt - 1, from registers
@@ -760,7 +698,7 @@ void k_nuts_iters(RandArgs a) {
         }                                               // (release, :735-736: nothing to free)
       }
     }
-    NUTS_PHASE(5);
+    NUTS_TIMER(t_ph, 5);
     if (later && !reject) {                             // progressive sampling (:743-751)
       const auto w = TreeWeights::add_point(E_max_now, pi_new, E_tmp);
       E_max_now = w.E_max_now;
@@ -773,7 +711,7 @@ void k_nuts_iters(RandArgs a) {
       sub_end = k == Lsub;
     }
     if (act && reject) state = S_ITER_END;               // q = live_point_q_old (:649, :731)
-    NUTS_PHASE(6);
+    NUTS_TIMER(t_ph, 6);
 
     // ================= sub-tree end: boundary, biased acceptance, termination (:757-784)
     // The other end (q, p, g) is loaded here for the termination dots; a next doubling towards it
@@ -837,7 +775,7 @@ void k_nuts_iters(RandArgs a) {
         state = S_READY;
       }
     }
-    NUTS_PHASE(7);
+    NUTS_TIMER(t_ph, 7);
   }
 #ifdef HMC_DEBUG_HOOKS
   if (a.stamps && lane == 0 && wv < n_waves) {   // g_stamps has one row per workspace wave
@@ -868,106 +806,80 @@ void k_nuts_iters(RandArgs a) {
   }
 }
 
+// The k_nuts_iters instance that runs these arguments (null: none compiled).
 template <int MT, bool EXACT>
-hipError_t launch_nuts_mt3(const RandArgs& args, bool gen, bool replay, hipStream_t s);
+auto nuts_iters_instance(const RandArgs& a, bool gen, bool replay) -> void (*)(RandArgs) {
+#ifdef HMC_NUTS_DEV_C5
+  // dev-only build of the c5 instance alone (seconds, not minutes) for ISA checks: any other shape is refused
+  if constexpr (MT == 7 && !EXACT) return k_nuts_iters<MT, EXACT, false, false, false, kShortAlways>;
+  return nullptr;
+#else
+  if (a.minvf) return replay ? k_nuts_iters<MT, EXACT, true, true, true> : k_nuts_iters<MT, EXACT, true, false, true>;
+  if (gen) return replay ? k_nuts_iters<MT, EXACT, true, true> : k_nuts_iters<MT, EXACT, true, false>;
+  if constexpr (MT == 7) {
+    if (a.D <= 16 * (MT - 1) + 4)                       // D = 97..100 (c5: D = 100)
+      return replay ? k_nuts_iters<MT, EXACT, false, true, false, kShortAlways>
+                    : k_nuts_iters<MT, EXACT, false, false, false, kShortAlways>;
+  }
+  return replay ? k_nuts_iters<MT, EXACT, false, true> : k_nuts_iters<MT, EXACT, false, false>;
+#endif
+}
 
-// Launches of at most kNutsMomIters iterations, each after its momenta (Philox, diagonal cov_p).
+// Philox momenta with a diagonal cov_p are drawn ahead: launches of at most kNutsMomIters
+// iterations, each after its momenta.  Replay and a full cov_p take the range in one launch.
 template <int MT, bool EXACT>
-hipError_t launch_nuts_mt2(const RandArgs& args, bool gen, bool replay, hipStream_t s) {
-  if (replay || args.minvf) return launch_nuts_mt3<MT, EXACT>(args, gen, replay, s);
-  const int64_t n_waves = (args.n + 15) / 16;
-  const int64_t wave_doubles = (int64_t)(V_SLOTS + 2 * (args.d_max + 1)) * 4 * MT * kWave;
-  double* pm = args.ws + n_waves * wave_doubles + n_waves * 16 + nuts_queue_bytes(args.n) / 8;
-  for (int i0 = args.it0; i0 < args.it1; i0 += kNutsMomIters) {
+hipError_t launch_nuts_mt(const RandArgs& args, bool gen, bool replay, hipStream_t s) {
+  const auto kernel = nuts_iters_instance<MT, EXACT>(args, gen, replay);
+  if (!kernel) return hipErrorInvalidValue;
+  const NutsTreeLayout L{args.n, MT, args.d_max, 0};
+  const bool drawn_ahead = !replay && !args.minvf;
+  // persistent: one block per CU (LDS: P + index tables), chains handed out by the queue
+  const int64_t blocks = (args.n + 16 * kNutsWaves - 1) / (16 * kNutsWaves);
+  const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)device_cus())));
+  const size_t lds = (size_t)MT * 4 * MT * kWave * sizeof(double);
+  const int per_launch = drawn_ahead ? kNutsMomIters : args.it1 - args.it0;
+  for (int i0 = args.it0; i0 < args.it1; i0 += per_launch) {
     RandArgs a = args;
     a.it0 = i0;
-    a.it1 = std::min(args.it1, i0 + kNutsMomIters);
-    const int64_t slots = a.n * (a.it1 - a.it0) * (8 * MT);
-    const dim3 mgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>((slots + 255) / 256, (int64_t)device_cus() * 8)));
-#ifndef HMC_NUTS_DEV_C5
-    if (gen) k_nuts_momenta<MT, true><<<mgrid, 256, 0, s>>>(a, pm);
-    else
-#endif
-      k_nuts_momenta<MT, false><<<mgrid, 256, 0, s>>>(a, pm);
+    a.it1 = std::min(args.it1, i0 + per_launch);
+    if (drawn_ahead) {
+      const int64_t slots = a.n * (a.it1 - a.it0) * (8 * MT);
+      const dim3 mgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>((slots + 255) / 256, (int64_t)device_cus() * 8)));
+      if (gen) k_nuts_momenta<MT, true><<<mgrid, 256, 0, s>>>(a, a.ws + L.momenta());
+      else k_nuts_momenta<MT, false><<<mgrid, 256, 0, s>>>(a, a.ws + L.momenta());
+      if (hipError_t e = hipGetLastError()) return e;
+    }
+    if (hipError_t e = hipMemsetAsync(a.ws + L.queue(), 0, L.queue_bytes(), s)) return e;
+    // chain affinity: all but the launch's last kNutsTail iterations run in kNutsBlock-tree units
+    a.nuts_kb = std::max(0, (a.it1 - a.it0) - kNutsTail);
+    a.wait_cap = nuts_wait_cap((int64_t)grid.x * kNutsWaves * 16, a.n, a.d_max, std::min(a.nuts_kb, kNutsBlock));
+    kernel<<<grid, 64 * kNutsWaves, lds, s>>>(a);
     if (hipError_t e = hipGetLastError()) return e;
-    if (hipError_t e = launch_nuts_mt3<MT, EXACT>(a, gen, replay, s)) return e;
   }
   return hipSuccess;
 }
 
-template <int MT, bool EXACT>
-hipError_t launch_nuts_mt3(const RandArgs& args, bool gen, bool replay, hipStream_t s) {
-  RandArgs a = args;
-  // persistent: one block per CU (LDS: P + index tables), chains handed out by the queue
-  const int64_t blocks = (a.n + 16 * kNutsWaves - 1) / (16 * kNutsWaves);
-  const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)device_cus())));
-  const int64_t n_waves = (a.n + 15) / 16;
-  const int64_t wave_doubles = (int64_t)(V_SLOTS + 2 * (a.d_max + 1)) * 4 * MT * kWave;
-  double* queue = a.ws + n_waves * wave_doubles + n_waves * 16;   // queue head, (unused), done[n]
-  if (hipError_t e = hipMemsetAsync(queue, 0, nuts_queue_bytes(a.n), s)) return e;
-  // chain affinity: all but the launch's last kNutsTail iterations run in kNutsBlock-tree units
-  a.nuts_kb = kNutsBlock > 1 ? std::max(0, (a.it1 - a.it0) - kNutsTail) : 0;
-  a.wait_cap = nuts_wait_cap((int64_t)grid.x * kNutsWaves * 16, a.n, a.d_max, std::min(a.nuts_kb, kNutsBlock));
-  const size_t lds = (size_t)MT * 4 * MT * kWave * sizeof(double);
-#ifdef HMC_NUTS_DEV_C5
-  if constexpr (MT == 7 && !EXACT) k_nuts_iters<MT, EXACT, false, false, false, kShortAlways><<<grid, 64 * kNutsWaves, lds, s>>>(a);
-  return hipGetLastError();
-#endif
-  if (a.minvf) {
-    if (replay) k_nuts_iters<MT, EXACT, true, true, true><<<grid, 64 * kNutsWaves, lds, s>>>(a);
-    else k_nuts_iters<MT, EXACT, true, false, true><<<grid, 64 * kNutsWaves, lds, s>>>(a);
-  } else if (gen) {
-    if (replay) k_nuts_iters<MT, EXACT, true, true><<<grid, 64 * kNutsWaves, lds, s>>>(a);
-    else k_nuts_iters<MT, EXACT, true, false><<<grid, 64 * kNutsWaves, lds, s>>>(a);
-  } else {
-    bool done = false;
-    if constexpr (MT == 7) {
-      if (a.D <= 16 * (MT - 1) + 4) {                   // D = 97..100 (c5: D = 100)
-        if (replay) k_nuts_iters<MT, EXACT, false, true, false, kShortAlways><<<grid, 64 * kNutsWaves, lds, s>>>(a);
-        else k_nuts_iters<MT, EXACT, false, false, false, kShortAlways><<<grid, 64 * kNutsWaves, lds, s>>>(a);
-        done = true;
-      }
-    }
-    if (!done) {
-      if (replay) k_nuts_iters<MT, EXACT, false, true><<<grid, 64 * kNutsWaves, lds, s>>>(a);
-      else k_nuts_iters<MT, EXACT, false, false><<<grid, 64 * kNutsWaves, lds, s>>>(a);
-    }
-  }
-  return hipGetLastError();
-}
-
 template <int MT>
-hipError_t launch_nuts_mt(const RandArgs& a, bool exact, bool gen, bool replay, hipStream_t s) {
-  return exact ? launch_nuts_mt2<MT, true>(a, gen, replay, s) : launch_nuts_mt2<MT, false>(a, gen, replay, s);
+hipError_t launch_nuts_tiles(const RandArgs& a, bool exact, bool gen, bool replay, hipStream_t s) {
+  return exact ? launch_nuts_mt<MT, true>(a, gen, replay, s) : launch_nuts_mt<MT, false>(a, gen, replay, s);
 }
 
 }  // namespace
 
 int64_t nuts_ws_doubles(int64_t n, int D, int d_max, int mom_iters) {
-  const int MT = dense_tiles(D);
-  const int64_t waves = (n + 15) / 16;
-  // vectors + tape cursors + work queue (head, spare, per-chain iterations done) + the Philox
-  // momenta drawn ahead (diagonal cov_p only) for min(32, iterations per call) iterations
-  return waves * (int64_t)(V_SLOTS + 2 * (d_max + 1)) * 4 * MT * kWave + waves * 16 + nuts_queue_bytes(n) / 8 +
-         nuts_mom_doubles(n, MT, mom_iters);
+  return NutsTreeLayout{n, dense_tiles(D), d_max, mom_iters}.total();
 }
 
-#ifdef HMC_NUTS_DEV_C5
-// dev-only build of the c5 instance alone (seconds instead of minutes per A/B compile): objdump /
-// register checks; not a usable library
-hipError_t launch_nuts_iters(const RandArgs& a, bool, bool, hipStream_t s) { return launch_nuts_mt2<7, false>(a, false, false, s); }
-#else
 hipError_t launch_nuts_iters(const RandArgs& a, bool exact, bool replay, hipStream_t s) {
   const bool gen = a.q0 || a.minv || a.pscale || a.dtv || a.minvf;
   switch (dense_tiles(a.D)) {
-    case 1: return launch_nuts_mt<1>(a, exact, gen, replay, s);
-    case 2: return launch_nuts_mt<2>(a, exact, gen, replay, s);
-    case 4: return launch_nuts_mt<4>(a, exact, gen, replay, s);
-    case 7: return launch_nuts_mt<7>(a, exact, gen, replay, s);
-    case 8: return launch_nuts_mt<8>(a, exact, gen, replay, s);
+    case 1: return launch_nuts_tiles<1>(a, exact, gen, replay, s);
+    case 2: return launch_nuts_tiles<2>(a, exact, gen, replay, s);
+    case 4: return launch_nuts_tiles<4>(a, exact, gen, replay, s);
+    case 7: return launch_nuts_tiles<7>(a, exact, gen, replay, s);
+    case 8: return launch_nuts_tiles<8>(a, exact, gen, replay, s);
   }
   return hipErrorInvalidValue;
 }
-#endif
 
 }  // namespace hmc

@@ -27,6 +27,7 @@
 // The triples then hold the kick vector in their g slot; P x lives in a per-chain scratch vector.
 #include "hmc_device.hpp"
 #include "hmc_internal.hpp"
+#include "hmc_nuts_layout.hpp"
 #include "hmc_nuts_tree.hpp"
 
 namespace hmc {
@@ -37,7 +38,7 @@ namespace {
 // points (old / new, :577 / :617), the d_max + 1 save slots' q and p (:623-626, :654-658), then
 // two scratch vectors of the full-cov_p products (P x of the newest point; inv_cov_p p or z)
 constexpr int kTriples = 3, kLive0 = 3 * kTriples, kSave0 = kLive0 + 2;
-__host__ __device__ constexpr int scratch0(int d_max) { return kSave0 + 2 * (d_max + 1); }
+static_assert(kSave0 == NutsChainLayout::kFixedVecs, "the save slots follow the layout's fixed vectors");
 
 __device__ __forceinline__ double q0_of(const RandArgs& a, int d) { return a.q0 ? a.q0[d] : 0.0; }
 __device__ __forceinline__ double minv_of(const RandArgs& a, int d) { return a.minv ? a.minv[d] : 1.0; }
@@ -148,10 +149,11 @@ __global__ __launch_bounds__(256) void k_nuts_big(RandArgs a, int Dp, int nv) {
   if (c >= a.n) return;
   const uint64_t gc = (uint64_t)(a.chain_offset + c);
   const int D = a.D, d_max = a.d_max;
-  const ChainVecs W{a.ws + c * (int64_t)nv * Dp, Dp};
-  double* gs = W.v(scratch0(a.d_max));       // P x of the newest point (full cov_p)
-  double* us = W.v(scratch0(a.d_max) + 1);   // inv_cov_p p, or the momentum's z (full cov_p)
-  int64_t* tcur = reinterpret_cast<int64_t*>(a.ws + a.n * (int64_t)nv * Dp);
+  const NutsChainLayout L{a.n, nv, Dp};
+  const ChainVecs W{a.ws + L.chain(c), Dp};
+  double* gs = W.v(L.scratch());       // P x of the newest point (full cov_p)
+  double* us = W.v(L.scratch() + 1);   // inv_cov_p p, or the momentum's z (full cov_p)
+  int64_t* tcur = reinterpret_cast<int64_t*>(a.ws + L.cursors());
   int64_t tpos = REPLAY ? tcur[c] : 0;
   double* qs = a.q + c * (int64_t)D;
   double Eprev = a.Eprev[c];
@@ -304,33 +306,22 @@ __global__ __launch_bounds__(256) void k_nuts_big(RandArgs a, int Dp, int nv) {
   }
 }
 
-int nuts_big_vectors(int d_max) { return scratch0(d_max) + 2; }
-int nuts_big_padded(int D) { return (D + kWave - 1) / kWave * kWave; }
-
 }  // namespace
 
-int64_t nuts_big_ws_doubles(int64_t n, int D, int d_max) {
-  return n * (int64_t)nuts_big_vectors(d_max) * nuts_big_padded(D) + n;   // vectors + tape cursors
-}
+int64_t nuts_big_ws_doubles(int64_t n, int D, int d_max) { return NutsChainLayout::of(n, D, d_max).total(); }
 
 hipError_t launch_nuts_big(const RandArgs& a, bool exact, bool replay, hipStream_t s) {
-  const int Dp = nuts_big_padded(a.D), nv = nuts_big_vectors(a.d_max);
+  const NutsChainLayout L = NutsChainLayout::of(a.n, a.D, a.d_max);
   const dim3 grid((unsigned)((a.n + 3) / 4));
+  void (*kernel)(RandArgs, int, int);
   if (a.minvf) {
-    if (exact) {
-      if (replay) k_nuts_big<true, true, true><<<grid, 256, 0, s>>>(a, Dp, nv);
-      else k_nuts_big<true, false, true><<<grid, 256, 0, s>>>(a, Dp, nv);
-    } else {
-      if (replay) k_nuts_big<false, true, true><<<grid, 256, 0, s>>>(a, Dp, nv);
-      else k_nuts_big<false, false, true><<<grid, 256, 0, s>>>(a, Dp, nv);
-    }
-  } else if (exact) {
-    if (replay) k_nuts_big<true, true, false><<<grid, 256, 0, s>>>(a, Dp, nv);
-    else k_nuts_big<true, false, false><<<grid, 256, 0, s>>>(a, Dp, nv);
+    if (exact) kernel = replay ? k_nuts_big<true, true, true> : k_nuts_big<true, false, true>;
+    else kernel = replay ? k_nuts_big<false, true, true> : k_nuts_big<false, false, true>;
   } else {
-    if (replay) k_nuts_big<false, true, false><<<grid, 256, 0, s>>>(a, Dp, nv);
-    else k_nuts_big<false, false, false><<<grid, 256, 0, s>>>(a, Dp, nv);
+    if (exact) kernel = replay ? k_nuts_big<true, true, false> : k_nuts_big<true, false, false>;
+    else kernel = replay ? k_nuts_big<false, true, false> : k_nuts_big<false, false, false>;
   }
+  kernel<<<grid, 256, 0, s>>>(a, L.Dp, L.nvec);
   return hipGetLastError();
 }
 

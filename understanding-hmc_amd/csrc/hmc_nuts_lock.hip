@@ -31,14 +31,13 @@
 
 #include "hmc_device.hpp"
 #include "hmc_internal.hpp"
+#include "hmc_nuts_layout.hpp"
 #include "hmc_nuts_tree.hpp"
 
 namespace hmc {
 
 namespace {
 
-constexpr int kLockW = 16;        // chain slots (waves) per block
-constexpr int kLockJ = 5;         // coordinates per lane: D <= 64 * kLockJ
 constexpr int kLockDmax = 64 * kLockJ;
 constexpr int kLockXS = 17;       // LDS row stride (doubles) of X[k][chain] and the partial tiles
 constexpr int kLockSegMax = 40;   // partial output tiles per block step (<= NT + 15)
@@ -46,7 +45,7 @@ constexpr int kLockPF = 4;        // precision fragments in flight per wave
 
 // slot vectors: left end (q, p, g), right end (q, p, g), live points, then save slot s: q, p
 enum : int { LV_LEFT = 0, LV_RIGHT = 3, LV_LIVE = 6, LV_SAVE = 8 };
-__host__ __device__ inline int lock_nvec(int d_max) { return LV_SAVE + 2 * (d_max + 1); }
+static_assert(LV_SAVE == NutsLockLayout::kFixedVecs, "the save slots follow the layout's fixed vectors");
 
 enum : int { LS_FETCH = 0, LS_GRAD = 1, LS_LEAP = 2, LS_DONE = 3 };
 
@@ -55,7 +54,7 @@ struct LockGeom {
   const double* pf;               // precision fragments [F][64]
   const double* mf;               // MASS: inv_cov_p fragments [F][64]
   const double* cf;               // MASS, Philox: chol(cov_p) fragments [F][64]
-  double* slots;                  // per slot: lock_nvec vectors of 64 * kLockJ doubles
+  double* slots;                  // the workspace's slot region (NutsLockLayout)
   unsigned long long* queue;      // next chain of the launch (zeroed per launch)
   int64_t* tcur;                  // per chain replay-tape cursor (persists across launches)
 };
@@ -93,11 +92,13 @@ __global__ __launch_bounds__(64 * kLockW) void k_nuts_lock(RandArgs a, LockGeom 
   const int D = a.D, d_max = a.d_max;
   const int KS = G.KS, F = G.F;
   const int Dp = 64 * J;
+  static_assert(J <= kLockJ, "a workspace slot is sized for 64 kLockJ doubles per vector (NutsLockLayout)");
   // every per-lane access goes through a buffer descriptor (scalar base) with the lane offset
   // lane * 8 and a constant 512 j: no 64-bit address per (array, j) kept live (the 128-register
   // budget of 16 waves per block spilled them)
-  double* const ws = G.slots + ((int64_t)blockIdx.x * kLockW + w) * (int64_t)lock_nvec(d_max) * Dp;
-  const __amdgpu_buffer_rsrc_t rws = __builtin_amdgcn_make_buffer_rsrc(ws, 0, lock_nvec(d_max) * Dp * 8, 0x00020000);
+  double* const ws = G.slots + ((int64_t)blockIdx.x * kLockW + w) * (int64_t)NutsLockLayout::nvec(d_max) * Dp;
+  const __amdgpu_buffer_rsrc_t rws =
+      __builtin_amdgcn_make_buffer_rsrc(ws, 0, NutsLockLayout::nvec(d_max) * Dp * 8, 0x00020000);
   const int lo8 = lane * 8;
   const __amdgpu_buffer_rsrc_t rpf = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(G.pf), 0, G.F * 512,
                                                                       0x00020000);
@@ -624,33 +625,23 @@ int64_t lock_blocks(int64_t n) {
 
 bool nuts_lock_path(int D) { return D > 128 && D <= kLockDmax; }
 
-// workspace: slot vectors (blocks x 16 slots), precision fragments, queue word, tape cursors
-// (mass: the inv_cov_p and chol(cov_p) fragments too)
-int64_t nuts_lock_ws_doubles(int64_t n, int D, int d_max, bool mass) {
-  const int NT = (D + 15) / 16, KS = (D + 3) / 4;
-  const int64_t blocks = (n + kLockW - 1) / kLockW < 1024 ? (n + kLockW - 1) / kLockW : 1024;
-  return (blocks < 1 ? 1 : blocks) * kLockW * (int64_t)lock_nvec(d_max) * 64 * kLockJ +
-         (int64_t)NT * KS * 64 * (mass ? 3 : 1) + 2 + n;
-}
+int64_t nuts_lock_ws_doubles(int64_t n, int D, int d_max, bool mass) { return NutsLockLayout(n, D, d_max, mass).total; }
 
 hipError_t launch_nuts_lock(const RandArgs& a, bool exact, bool replay, hipStream_t s) {
-  LockGeom g{};
-  g.NT = (a.D + 15) / 16;
-  g.KS = (a.D + 3) / 4;
-  g.F = g.NT * g.KS;
-  int64_t blocks = lock_blocks(a.n);
-  const int64_t cap = (a.n + kLockW - 1) / kLockW < 1024 ? (a.n + kLockW - 1) / kLockW : 1024;
-  if (blocks > cap) blocks = cap < 1 ? 1 : cap;             // (the workspace holds this many slots)
-  const int64_t slot_doubles = (cap < 1 ? 1 : cap) * kLockW * (int64_t)lock_nvec(a.d_max) * 64 * kLockJ;
-  g.slots = a.ws;
-  double* pf = a.ws + slot_doubles;
-  g.pf = pf;
   const bool mass = a.minvf != nullptr;
-  double* const after = pf + (int64_t)g.F * 64 * (mass ? 3 : 1);
-  g.mf = mass ? pf + (int64_t)g.F * 64 : nullptr;
-  g.cf = (mass && !replay) ? pf + 2 * (int64_t)g.F * 64 : nullptr;
-  g.queue = reinterpret_cast<unsigned long long*>(after);
-  g.tcur = reinterpret_cast<int64_t*>(after + 2);
+  const NutsLockLayout L(a.n, a.D, a.d_max, mass);
+  const int64_t blocks = std::min(lock_blocks(a.n), L.blocks);   // (the workspace holds L.blocks slot blocks)
+  LockGeom g{};
+  g.NT = L.NT;
+  g.KS = L.KS;
+  g.F = L.F;
+  g.slots = a.ws;
+  double* const pf = a.ws + L.pf;
+  g.pf = pf;
+  g.mf = mass ? a.ws + L.mf : nullptr;
+  g.cf = (mass && !replay) ? a.ws + L.cf : nullptr;
+  g.queue = reinterpret_cast<unsigned long long*>(a.ws + L.queue);
+  g.tcur = reinterpret_cast<int64_t*>(a.ws + L.cursors);
   // the partial tiles of one block step: NT plus one per wave boundary inside a tile
   if (g.NT + kLockW - 1 > kLockSegMax || a.D > kLockDmax) return hipErrorInvalidValue;
   if (hipError_t e = hipMemsetAsync(g.queue, 0, sizeof(unsigned long long), s)) return e;
