@@ -499,6 +499,55 @@ hmc_status hmc_glm_nuts_iters_adapt(const hmc_glm* m, const hmc_kinetic* k, cons
                                     const hmc_replay* r, hmc_state* st, void* workspace, int64_t workspace_bytes,
                                     const hmc_adapt* ad, void* stream);
 
+/* ---------------------------------------------------------------- posterior predictive (GLM)
+ * What a stored run predicts at a set of rows, and how well it predicts the data it was fitted on
+ * (lppd, p_waic and WAIC of Gelman, Hwang & Vehtari 2014), reduced on the device: one read of the
+ * samples, HMC_PRED_STRIDE numbers per evaluation row back.  For every evaluation row j of `eval`
+ * (X [n][ldx], y [n] or NULL, family; prior_prec is ignored and may be NULL) and every sample s,
+ * from z = x_j . q_s (f64 matrix cores, hmc_pred.hip):
+ *   HMC_GLM_BERNOULLI  mu = sigma(z),  ll = y z - softplus(z)   (the overflow-free forms above)
+ *   HMC_GLM_POISSON    mu = exp(z),    ll = y z - exp(z)        (without -lgamma(y + 1): constant
+ *                                                                in s, the caller adds it)
+ * Samples are read in place from a strided view: element (chain c, row r, dim d) at
+ * q[c*chain_stride + r*row_stride + d], rows row_begin, row_begin + row_step, ... < row_end of
+ * every chain; S = n_chains x rows-per-chain samples in all.
+ * out[n][HMC_PRED_STRIDE], one record per evaluation row, moments over all S samples:
+ *   0 n          sample count S, as a double
+ *   1 mu_mean    mean of mu            2 mu_M2   sum (mu - mu_mean)^2
+ *   3 ll_mean    mean of ll            4 ll_M2   sum (ll - ll_mean)^2
+ *   5 ll_max     max of ll             6 ll_sumexp   sum exp(ll - ll_max)
+ *   7 reserved, written 0
+ * With y == NULL slots 3-6 are NaN.  Records of disjoint sample sets (shards, ranks) merge: Chan's
+ * rule for (n, mean, M2), the rescaled sum for (max, sumexp); csrc/hmc_pred.hpp states the rule
+ * once and hmc_amd.predictive.merge_partials restates it.  The moments are one-pass sums about a
+ * per-lane pivot (a lane's first value), which do not cancel as sum x^2 - (sum x)^2 / n does.
+ * Non-finite values follow NumPy: a sample with mu = +inf gives mu_mean = +inf, mu_M2 = NaN,
+ *   ll_mean = -inf, ll_M2 = NaN, while ll_max and ll_sumexp ignore the -inf term (every ll -inf:
+ *   ll_max = -inf, ll_sumexp = 0); a NaN z makes every slot but 0 and 7 NaN.  A non-finite
+ *   evaluation row changes no bit of any other row.
+ * Launch: (groups of 64 evaluation rows) x (sample blocks); every sample block writes its records
+ *   to the workspace and a second kernel merges them in block order.  No floating-point atomics:
+ *   results are bit-reproducible.  hmc_glm_predictive_blocks is the number of sample blocks, a
+ *   function of (D, n, S) alone (0: unsupported shape or S < 1), and
+ *   hmc_glm_predictive_workspace_size = blocks x n x HMC_PRED_STRIDE doubles, in bytes.
+ * HMC_EINVAL: NULL eval, s, X, q or out; D < 1, n < 0, ldx < D, row_stride < D; row_step < 1,
+ *   row_begin < 0, row_end < row_begin or n_chains < 0; an unknown family; a NULL workspace or
+ *   workspace_bytes below the size query.  HMC_ENOTSUP: D > HMC_LOGIT_MAX_D, n > HMC_LOGIT_MAX_N.
+ *   All checks run on the host before any launch.  n == 0 or S == 0: HMC_OK, nothing is launched
+ *   and out is untouched (workspace may then be NULL). */
+enum { HMC_PRED_STRIDE = 8 };
+typedef struct hmc_samples {
+  const double* q;            /* element (c, r, d) at q[c*chain_stride + r*row_stride + d]    */
+  int64_t n_chains, chain_stride, row_stride;   /* row_stride >= D                            */
+  int64_t row_begin, row_end, row_step;         /* rows row_begin, row_begin + row_step, ...
+                                                   < row_end; row_step >= 1                   */
+} hmc_samples;                /* 56 bytes: offsets 0, 8, 16, 24, 32, 40, 48                  */
+
+int64_t hmc_glm_predictive_workspace_size(int32_t D, int64_t n_eval, int64_t n_samples);
+int32_t hmc_glm_predictive_blocks(int32_t D, int64_t n_eval, int64_t n_samples);
+hmc_status hmc_glm_predictive(const hmc_glm* eval, const hmc_samples* s, double* out, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+
 /* The standard normals the Philox mode draws for (chain, iteration): out[n][2*npairs].
  * Debug/verification entry (statistical tests of the in-kernel generator). */
 hmc_status hmc_rng_normals(uint64_t seed, int64_t chain0, int64_t n, int32_t iteration,

@@ -15,6 +15,7 @@
 #include "hmc_internal.hpp"
 #include "hmc_logit.hpp"
 #include "hmc_mix.hpp"
+#include "hmc_pred.hpp"
 
 namespace {
 
@@ -961,6 +962,47 @@ hmc_status hmc_glm_nuts_iters_adapt(const hmc_glm* m, const hmc_kinetic* k, cons
   const char* what = "hmc_glm_nuts_iters_adapt";
   if (hmc_status e = check_adapt(ad, what)) return e;
   return glm_nuts_iters(m, k, s, r, st, workspace, workspace_bytes, stream, what, ad);
+}
+
+// ---------------------------------------------------------------- posterior predictive (GLM)
+int32_t hmc_glm_predictive_blocks(int32_t D, int64_t n_eval, int64_t n_samples) {
+  return (int32_t)hmc::pred_sample_blocks(D, n_eval, n_samples);
+}
+
+int64_t hmc_glm_predictive_workspace_size(int32_t D, int64_t n_eval, int64_t n_samples) {
+  return hmc::pred_sample_blocks(D, n_eval, n_samples) * n_eval * HMC_PRED_STRIDE * (int64_t)sizeof(double);
+}
+
+hmc_status hmc_glm_predictive(const hmc_glm* eval, const hmc_samples* s, double* out, void* workspace,
+                              int64_t workspace_bytes, void* stream) {
+  const char* what = "hmc_glm_predictive";
+  if (!eval || !s) return fail(HMC_EINVAL, "%s: null evaluation set / sample set", what);
+  if (!eval->X || !s->q || !out) return fail(HMC_EINVAL, "%s: null X, q or out", what);
+  if (eval->family != HMC_GLM_BERNOULLI && eval->family != HMC_GLM_POISSON)
+    return fail(HMC_EINVAL, "%s: unknown family %d (HMC_GLM_BERNOULLI, HMC_GLM_POISSON)", what, eval->family);
+  if (eval->D < 1 || eval->n < 0) return fail(HMC_EINVAL, "%s: D must be >= 1 and n >= 0", what);
+  if (eval->ldx < eval->D) return fail(HMC_EINVAL, "%s: ldx=%lld < D=%d", what, (long long)eval->ldx, eval->D);
+  if (s->row_stride < eval->D)
+    return fail(HMC_EINVAL, "%s: row_stride=%lld < D=%d", what, (long long)s->row_stride, eval->D);
+  if (s->row_step < 1) return fail(HMC_EINVAL, "%s: row_step=%lld must be >= 1", what, (long long)s->row_step);
+  if (s->row_begin < 0 || s->row_end < s->row_begin || s->n_chains < 0)
+    return fail(HMC_EINVAL, "%s: rows [%lld, %lld) of %lld chains", what, (long long)s->row_begin,
+                (long long)s->row_end, (long long)s->n_chains);
+  if (eval->D > HMC_LOGIT_MAX_D)
+    return fail(HMC_ENOTSUP, "%s: D=%d, the kernel takes D <= %d", what, eval->D, HMC_LOGIT_MAX_D);
+  if (eval->n > HMC_LOGIT_MAX_N)
+    return fail(HMC_ENOTSUP, "%s: n=%d, the kernel takes n <= %d", what, eval->n, HMC_LOGIT_MAX_N);
+  const int64_t rows = (s->row_end - s->row_begin + s->row_step - 1) / s->row_step;
+  if (rows > 0 && s->n_chains > INT64_MAX / rows) return fail(HMC_EINVAL, "%s: chains x rows overflows", what);
+  const int64_t n_samples = s->n_chains * rows;
+  if (eval->n == 0 || n_samples == 0) return HMC_OK;   // nothing to reduce: out stays as it is
+  const int64_t need = hmc_glm_predictive_workspace_size(eval->D, eval->n, n_samples);
+  if (!workspace) return fail(HMC_EINVAL, "%s: null workspace", what);
+  if (workspace_bytes < need)
+    return fail(HMC_EINVAL, "%s: workspace of %lld bytes, D=%d, %d rows, %lld samples need %lld "
+                "(hmc_glm_predictive_workspace_size)", what, (long long)workspace_bytes, eval->D, eval->n,
+                (long long)n_samples, (long long)need);
+  return hip_status(hmc::launch_pred(*eval, *s, rows, n_samples, out, (double*)workspace, (hipStream_t)stream), what);
 }
 
 hmc_status hmc_rng_normals(uint64_t seed, int64_t chain0, int64_t n, int32_t iteration, int32_t npairs, double* out,

@@ -83,6 +83,17 @@ class Adapt(ctypes.Structure):
                 ("gamma", ctypes.c_double), ("t0", ctypes.c_double), ("kappa", ctypes.c_double)]
 
 
+PRED_STRIDE = 8    # include/hmc.h HMC_PRED_STRIDE: doubles of one predictive record
+(PRED_N, PRED_MU_MEAN, PRED_MU_M2, PRED_LL_MEAN, PRED_LL_M2, PRED_LL_MAX, PRED_LL_SUMEXP, PRED_RESERVED) = range(8)
+
+
+class Samples(ctypes.Structure):
+    """hmc_samples: a strided view of stored samples (device pointer) and the rows to read."""
+    _fields_ = [("q", c_dp), ("n_chains", ctypes.c_int64), ("chain_stride", ctypes.c_int64),
+                ("row_stride", ctypes.c_int64), ("row_begin", ctypes.c_int64), ("row_end", ctypes.c_int64),
+                ("row_step", ctypes.c_int64)]
+
+
 # Exported symbols (tests check every one of these is present; keep in sync with include/hmc.h)
 SYMBOLS = {
     "hmc_version": (ctypes.c_char_p, []),
@@ -160,6 +171,10 @@ SYMBOLS = {
                                                 ctypes.POINTER(Schedule), ctypes.POINTER(Replay),
                                                 ctypes.POINTER(State), c_dp, ctypes.c_int64,
                                                 ctypes.POINTER(Adapt), c_dp]),
+    "hmc_glm_predictive_workspace_size": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64]),
+    "hmc_glm_predictive_blocks": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64]),
+    "hmc_glm_predictive": (ctypes.c_int, [ctypes.POINTER(GLM), ctypes.POINTER(Samples), c_dp, c_dp, ctypes.c_int64,
+                                          c_dp]),
     "hmc_rng_normals": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                        ctypes.c_int32, c_dp, c_dp]),
     "hmc_philox": (ctypes.c_int, [ctypes.c_uint32] * 6 + [ctypes.c_int64, c_dp, c_dp]),

@@ -386,6 +386,40 @@ class HMC_sampler(sampler):
             return
         sampler.compute_convergence_stats(self)
 
+    # ------------------------------------------------------------------ posterior predictive / WAIC
+    def _predictive_partials(self, X, y, what):
+        """Records of hmc_amd.predictive over rows 1.. of every chain (the start row is dropped, as
+        compute_convergence_stats does): from q_chain_device where the run left it, else q_chain."""
+        from . import predictive as P
+        t = self._target
+        if not isinstance(t, GLMTarget):
+            raise NotImplementedError("%s is supported for a GLMTarget only" % what)
+        src = getattr(self, "q_chain_device", None)
+        if src is None and getattr(self, "engine", None) is not None:
+            src = self.q_chain
+        if src is None:
+            raise RuntimeError("%s needs the samples of a run: call gen_sample first (with store_chain)" % what)
+        return P.glm_predictive_partials(X, y, t.family, src, rows=slice(1, None), device=self.device)
+
+    def posterior_predictive(self, X_new=None):
+        """Posterior predictive mean and variance of a new observation at the rows X_new (n_eval, D)
+        (default: the target's own X), reduced on the device (hmc_amd.predictive): a dict with n,
+        mean and var per row.  GLMTarget only; after gen_sample."""
+        from . import predictive as P
+        t = self._target
+        X = t.X if (X_new is None and isinstance(t, GLMTarget)) else X_new
+        part = self._predictive_partials(X, None, "posterior_predictive")
+        return P.finish(part, None, t.family)
+
+    def waic(self):
+        """lppd, p_waic, elpd_waic, waic = -2 elpd_waic and its standard error on the data the target
+        was fitted on (Gelman, Hwang & Vehtari 2014), with the per-row terms (hmc_amd.predictive.finish).
+        GLMTarget only; after gen_sample."""
+        from . import predictive as P
+        t = self._target
+        part = self._predictive_partials(getattr(t, "X", None), getattr(t, "y", None), "waic")
+        return P.finish(part, t.y, t.family)
+
     def _finish(self, eng, elapsed, verbose):
         """Copy results to the reference's NumPy attributes and derive the counters."""
         c = eng.read_counters()
