@@ -5,22 +5,30 @@
 // another layout: chain 4 * wave + r lives in the 16-lane DPP row r, and lane s of the row holds
 // coordinates s + 16 j, j < 7 (slots past D hold exact zeros).  What the wave kernel pays once per
 // wave (the energy reduction, the accept test, parking, tallies, addresses) is paid once per four
-// chains here.  Every q is bit-identical to the wave kernel's; the energies are row sums
-// (row_shr 1/2/4/8) instead of the full-wave sum, so E and dE move in the last bits.
+// chains here.  Every q is bit-identical to the wave kernel's; the energies are row sums (one
+// chain for both: a fold by eight lanes, then row_shr 1/2/4) instead of the full-wave sum, so E and
+// dE move in the last bits.
 //   * trajectory lengths differ per row: the paired-step loop runs to the wave's longest
-//     trajectory and rows that are done are switched off through EXEC;
-//   * the decision is formed in lane 15 of each row, the four bits are widened to row masks on the
-//     SALU, and a reject restores under that EXEC mask;
+//     trajectory (known since the 16-iteration draw of L) and rows that are done are switched off
+//     through EXEC;
+//   * the energy lands in lane 15 of each row and the decision is formed in lane 7; its four bits
+//     are widened to row masks on the SALU, and a reject restores under that EXEC mask;
 //   * momentum: every pass draws 16 consecutive pairs of each row's own (pair, iteration) stream
 //     into that chain's LDS ring (stream order, ten 128-B chunks; the first is mirrored behind the
-//     tenth, so that a read which starts in the last chunk runs on without a per-lane wrap).
+//     tenth, so that a read which starts in the last chunk runs on without a per-lane wrap).  The
+//     Philox block starts from a per-block table of what rounds 1-2 derive from the pair alone
+//     (hmc_philox_split.hpp); -DHMC_ROWS_NO_SPLIT keeps the whole block, for an A/B of the table.
 // Odd D needs no instance of its own: coordinates are read from the ring one by one, so the pair
 // that holds the dimension past D is only ever read by a masked slot.
-// Dynamic LDS: the Box–Muller tables (32 KB) + 8 waves x 4 chains x 1408 B = 76 KB per block: two
-// blocks per CU, four waves per SIMD (112 VGPRs, no scratch).  Two blocks rather than one of 16 waves:
-// a block's start-up (tables, state loads, first ring fill) and its tail then overlap the other's
-// iterations (measured 5% faster).
+// Dynamic LDS: the Box–Muller tables (32 KB) + the split-Philox table of the block's pairs (1 KB) +
+// 8 waves x 4 chains x 1408 B = 77 KB per block: two blocks per CU (154 of its 160 KB), four waves per
+// SIMD (no scratch).  Two blocks rather than one of 16 waves: a block's start-up (tables, state loads,
+// first ring fill) and its tail then overlap the other's iterations (measured 5% faster).
+// The kernel has no static LDS, so the dynamic allocation starts at LDS byte 0 (the launcher checks
+// it): every LDS address is formed as a 32-bit byte offset with the region's start as a constant,
+// which lands in the instruction's immediate offset instead of an add of the allocation's base.
 #include "hmc_device.hpp"
+#include "hmc_philox_split.hpp"
 #include "hmc_internal.hpp"
 #include "hmc_target_ops.hpp"
 
@@ -34,8 +42,21 @@ constexpr int kRowsBlock = 512;                    // 8 waves
 constexpr int kRowChunkBytes = 8 * kRowLanes;      // one slot of a row: 16 doubles
 constexpr uint32_t kRowRingBytes = 10 * kRowChunkBytes;   // per chain: at most (112 - 1) + 32 doubles wait in it
 constexpr uint32_t kRowRingAlloc = 11 * kRowChunkBytes;   // + the mirror of chunk 0 (reads end 248 B past a chunk's start)
-constexpr size_t kRowsLds =
-    8 * (size_t)kNormalTableDoubles + (size_t)(kRowsBlock / kWave) * kRowChains * kRowRingAlloc;
+constexpr int kRowMaxPairs = 56;                   // D <= 112
+constexpr uint32_t kRowSplitOff = 8 * kNormalTableDoubles;             // split-Philox table: behind the Box–Muller tables
+constexpr uint32_t kRowRingOff = kRowSplitOff + 1024;                  // 56 entries x 16 B, padded to 1 KB
+constexpr size_t kRowsLds = kRowRingOff + (size_t)(kRowsBlock / kWave) * kRowChains * kRowRingAlloc;
+static_assert(16 * kRowMaxPairs <= 1024 && kRowRingOff + kRowRingBytes + 16 * kRowLanes < 65536,
+              "the table fits its region and every region start fits the 16-bit immediate offset");
+static_assert(2 * kRowsLds <= 160 * 1024, "two blocks per CU");
+
+// LDS byte offset -> pointer (the offset is a run-time value for the language: no null constant)
+template <class T>
+__device__ __forceinline__ __attribute__((address_space(3))) T* lds_at(uint32_t off) {
+  return (__attribute__((address_space(3))) T*)(uintptr_t)off;
+}
+typedef uint32_t lds_u32x4 __attribute__((ext_vector_type(4)));
+typedef double lds_f64x2 __attribute__((ext_vector_type(2)));
 
 // x.x of the lane's coordinates, the chain hmc_wave.hip's wave_sumsq_fma forms
 template <int C>
@@ -47,20 +68,36 @@ __device__ __forceinline__ double rows_sumsq(const double (&v)[C], double s0) {
   return s;
 }
 
-// sums over each 16-lane row: lane 15 of the row holds the total (EXEC all ones)
-__device__ __forceinline__ double row_sum_l15(double v) {
+// DPP move of src into the lanes of the banks in BANK_MASK (four lanes each); the other lanes keep old
+template <int CTRL, int BANK_MASK>
+__device__ __forceinline__ double dpp_banks(double old, double src) {
+  const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(src), CTRL, 0xF, BANK_MASK, false);
+  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(src), CTRL, 0xF, BANK_MASK, false);
+  return __hiloint2double(hi, lo);
+}
+
+// Two sums over each 16-lane row in one chain (EXEC all ones): both are first folded by eight lanes
+// into one register, lo into lanes 0-7 (lo[i] + lo[i + 8]) and hi into lanes 8-15 (hi[i - 8] + hi[i]),
+// then row_shr 1/2/4 finish both at once: lane 7 of the row holds the total of lo, lane 15 that of hi.
+__device__ __forceinline__ double row_sum2_l7_l15(double lo, double hi) {
+  double o = __hiloint2double(__builtin_amdgcn_mov_dpp(__double2hiint(lo), 0x108, 0xF, 0x3, false),
+                              __builtin_amdgcn_mov_dpp(__double2loint(lo), 0x108, 0xF, 0x3, false));   // row_shl:8 -> lanes 0-7
+  o = dpp_banks<0x118, 0xC>(o, hi);                   // row_shr:8 -> lanes 8-15
+  double v = dpp_banks<0xE4, 0xC>(lo, hi);            // quad_perm:[0,1,2,3]: hi as it is in lanes 8-15
+  v += o;
   v += dpp_u<0x111>(v);        // row_shr:1 (bound_ctrl: lanes shifted in from outside the row read 0)
   v += dpp_u<0x112>(v);        // row_shr:2
   v += dpp_u<0x114>(v);        // row_shr:4
-  v += dpp_u<0x118>(v);        // row_shr:8
   return v;
 }
 
-// max of two wave-uniform values on the SALU (written in C the compiler takes it to the VALU)
-__device__ __forceinline__ int s_max_i32(int a, int b) {
-  int r;
-  asm("s_max_i32 %0, %1, %2" : "=s"(r) : "s"(a), "s"(b) : "scc");
-  return r;
+// sum over each 16-lane row of per-lane integer tallies: lane 15 of the row holds the total
+__device__ __forceinline__ uint32_t row_sum_u32_l15(uint32_t v) {
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, true);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, true);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, true);
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, true);
+  return v;
 }
 
 // n += 1 in the lanes of `mask` (one VALU: the mask is the carry-in)
@@ -69,22 +106,44 @@ __device__ __forceinline__ void add_mask(uint32_t& n, uint64_t mask) {
   asm("v_addc_co_u32_e64 %0, %1, %0, 0, %2" : "+v"(n), "=&s"(co) : "s"(mask));
 }
 
-// Parks v (valid in lane 15 of each row) by shifting each row of buf one lane down and taking v in
-// lane 15 (row_shl:1, the lane without a source keeps `old`): after n parks the values sit in lanes
-// 16 - n .. 15, oldest first.  No LDS round trip.
-__device__ __forceinline__ double park_row_shift(double buf, double v) {
-  const int lo = __builtin_amdgcn_update_dpp(__double2loint(v), __double2loint(buf), 0x101, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(__double2hiint(v), __double2hiint(buf), 0x101, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
+constexpr uint64_t kRowLane15 = 0x8000800080008000ull;   // lane 15 of every row
+constexpr uint64_t kRowLane7 = 0x0080008000800080ull;    // lane 7 of every row
+
+// Parks e in Ebuf and d in dEbuf (both valid in lane 15 of each row): each row of a buffer moves one
+// lane down and takes the value in lane 15, so after n parks the values sit in lanes 16 - n .. 15,
+// oldest first.  No LDS round trip.  One select per word, in place: the DPP operand is the buffer
+// shifted by row_shl:1 (lane 15 has no source and reads 0 under bound_ctrl), the select mask (VCC)
+// is lane 15 of every row, where the value is taken instead.  The buffers were last written by the
+// park before, so no DPP read follows a write of its register within the hazard's two wait states.
+__device__ __forceinline__ void park_rows(double& Ebuf, double& dEbuf, double e, double d, uint64_t lane15) {
+  int el = __double2loint(Ebuf), eh = __double2hiint(Ebuf), dl = __double2loint(dEbuf), dh = __double2hiint(dEbuf);
+  asm("s_mov_b64 vcc, %[m]\n\t"
+      "s_nop 1\n\t"
+      "v_cndmask_b32_dpp %[el], %[el], %[vel], vcc row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+      "v_cndmask_b32_dpp %[eh], %[eh], %[veh], vcc row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+      "v_cndmask_b32_dpp %[dl], %[dl], %[vdl], vcc row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+      "v_cndmask_b32_dpp %[dh], %[dh], %[vdh], vcc row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+      : [el] "+v"(el), [eh] "+v"(eh), [dl] "+v"(dl), [dh] "+v"(dh)
+      : [vel] "v"(__double2loint(e)), [veh] "v"(__double2hiint(e)), [vdl] "v"(__double2loint(d)),
+        [vdh] "v"(__double2hiint(d)), [m] "s"(lane15)
+      : "vcc");
+  Ebuf = __hiloint2double(eh, el);
+  dEbuf = __hiloint2double(dh, dl);
 }
 
 template <int C>
 __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_rows_iters(RandArgs a) {
   static_assert(C == 7, "seven coordinates per lane: D in (96, 112], only the last slot is partial");
-  extern __shared__ __attribute__((aligned(16))) double s_rows[];
-  double* const s_ntab = s_rows;                                     // Box–Muller tables
-  char* const ring_b = reinterpret_cast<char*>(s_rows + kNormalTableDoubles);
-  init_normal_tables(s_ntab);
+  const double* const s_ntab = (const double*)lds_at<double>(0);   // Box–Muller tables
+  init_normal_tables((double*)lds_at<double>(0));
+  // The split-Philox table of this block: entry k of pair k under the seed's high word and the high
+  // word of the block's first chain id.
+  constexpr int chains_per_block = (kRowsBlock / kWave) * kRowChains;
+  const uint32_t tab_ghi = (uint32_t)((uint64_t)(a.chain_offset + (int64_t)blockIdx.x * chains_per_block) >> 32);
+  if ((int)threadIdx.x < a.npairs) {
+    const uint4 e = split_entry(threadIdx.x, tab_ghi, a.k1);
+    *lds_at<lds_u32x4>(kRowSplitOff + 16u * threadIdx.x) = lds_u32x4{e.x, e.y, e.z, e.w};
+  }
   __syncthreads();
   const int lane = threadIdx.x & (kWave - 1);
   const int wib = threadIdx.x / kWave;
@@ -97,44 +156,62 @@ __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4
   const bool st6 = valid && v6;
   const uint64_t gc = (uint64_t)(a.chain_offset + c);
   const uint32_t ringrow = (uint32_t)(wib * kRowChains + r) * kRowRingAlloc;   // this chain's ring (bytes)
+  // The table serves a wave whose valid rows all have its high word (rows past the last chain are
+  // never stored: they may draw another chain's stream).  A wave with a row across a 2^32 boundary of
+  // the global chain id draws with draw_block instead; decided here once, uniform.
+#ifdef HMC_ROWS_NO_SPLIT
+  const bool split = false;
+#else
+  const bool split = __builtin_amdgcn_ballot_w64(valid && (uint32_t)(gc >> 32) != tab_ghi) == 0;
+#endif
+  uint32_t sp_a, sp_b;                                    // the lane's loop-invariant words of rounds 1-2
+  split_lane_words((uint32_t)gc, a.k0, sp_a, sp_b);
 
-  // Generator: lane s of a row draws pair gk of iteration git of its chain; a pass moves it 16 pairs
-  // on (npairs >= 49: one wrap at most).  gen_n: pairs drawn per chain, gposb: their ring position.
+  // Generator: lane s of a row draws pair gkb / 16 of iteration git of its chain; a pass moves it 16
+  // pairs on (npairs >= 49: one wrap at most).  The pair index is kept in bytes of the split table.
+  // gen_n: pairs drawn per chain, gposb: their ring position.
   int gen_n = 0;
   uint32_t gposb = 0;
-  uint32_t gk = s, git = a.it0;
+  uint32_t gkb = 16 * s, git = a.it0;
   const uint32_t wlane = ringrow + 16 * s;
   int rbaseb = 0;                                         // ring position (bytes) of the next iteration's doubles
   const int dpb = 16 * a.npairs;                          // stream bytes per iteration
   const uint32_t rlane = ringrow + 8 * s;
   double q[C], p[C], qi[C];
-  // 16 pairs on: gk += 16, and past the iteration's last pair gk -= npairs, git += 1 (four VALU: the
-  // borrow of gk - npairs picks both)
+  // 16 pairs on: gkb += 256, and past the iteration's last pair gkb -= 16 npairs, git += 1 (four VALU:
+  // the borrow of gkb - 16 npairs picks both)
   auto advance = [&](uint32_t& k, uint32_t& i) {
     uint64_t bo;
     uint32_t tk;
-    asm("v_add_u32_e32 %0, 16, %0\n\t"
+    asm("v_add_u32_e32 %0, 0x100, %0\n\t"
         "v_subrev_co_u32_e32 %2, vcc, %4, %0\n\t"
         "v_subb_co_u32_e64 %1, %3, %1, -1, vcc\n\t"
         "v_cndmask_b32_e32 %0, %2, %0, vcc"
         : "+v"(k), "+v"(i), "=&v"(tk), "=&s"(bo)
-        : "s"(a.npairs)
+        : "s"(dpb)
         : "vcc");
   };
   auto ring_momentum = [&](int it) {
     const int need = (it - a.it0 + 1) * a.npairs;
     while (gen_n < need) {                                // wave-uniform
       double z0, z1;
-      normal_pair_tab(draw_block(gk, git, gc, a.k0, a.k1), s_ntab, z0, z1);
+      uint4 blk;
+      if (split) {
+        const lds_u32x4 e = *lds_at<lds_u32x4>(kRowSplitOff + gkb);
+        blk = split_block(make_uint4(e.x, e.y, e.z, e.w), sp_a, sp_b, git, a.k0, a.k1);
+      } else {
+        blk = draw_block(gkb >> 4, git, gc, a.k0, a.k1);
+      }
+      normal_pair_tab(blk, s_ntab, z0, z1);
       // a pass fills two whole chunks (1280 = 5 * 256: it never straddles the wrap)
-      char* const w = ring_b + (gposb + wlane);
-      *reinterpret_cast<double2*>(w) = make_double2(z0, z1);
+      const uint32_t w = gposb + wlane;
+      *lds_at<lds_f64x2>(kRowRingOff + w) = lds_f64x2{z0, z1};
       // the mirror of chunk 0: the pass's first eight pairs
-      if (gposb == 0 && s < kRowLanes / 2) *reinterpret_cast<double2*>(w + kRowRingBytes) = make_double2(z0, z1);
+      if (gposb == 0 && s < kRowLanes / 2) *lds_at<lds_f64x2>(kRowRingOff + kRowRingBytes + w) = lds_f64x2{z0, z1};
       gen_n += kRowLanes;
       gposb += 16 * kRowLanes;
       if (gposb >= kRowRingBytes) gposb -= kRowRingBytes;
-      advance(gk, git);
+      advance(gkb, git);
     }
     __builtin_amdgcn_wave_barrier();
     // slot j starts in chunk (cb + j) mod 10 (SALU) and this lane reads ob + 8 s bytes on, possibly
@@ -145,7 +222,7 @@ __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4
     for (int j = 0; j < C; ++j) {
       uint32_t cj = cbb + kRowChunkBytes * j;
       if (cj >= kRowRingBytes) cj -= kRowRingBytes;
-      p[j] = *reinterpret_cast<const double*>(ring_b + (opaque_s32(cj) + a0));
+      p[j] = *lds_at<double>(kRowRingOff + (opaque_s32(cj) + a0));
     }
     p[C - 1] = v6 ? p[C - 1] : 0.0;                       // dimension past D: no such coordinate
     rbaseb += dpb;
@@ -163,6 +240,7 @@ __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4
 
   ring_momentum(a.it0);
   const double hlogc = 0.5 * a.logc;
+  const uint64_t lane15 = kRowLane15;
   double m0l = rows_sumsq<C>(q, 0.0);                    // this lane's part of q.q
   double e0l = rows_sumsq<C>(p, m0l);                    // ... and of q.q + p.p at the iteration start
   double E0 = 0.0;
@@ -188,12 +266,17 @@ __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4
       if (dEc) __builtin_nontemporal_store(dEbuf, dEc + (row_first - first));
     }
   };
-  uint32_t n_acc = 0, n_acc_wu = 0, n_lf = 0, n_lf2 = 0, n_oob = 0;   // per lane, the same in a row's lanes
-  int it_base = a.it0 - kRowLanes, draw_L = 0;
+  uint32_t n_acc = 0, n_acc_wu = 0, n_oob = 0;           // per lane, the same in a row's lanes
+  uint32_t n_lf = 0, n_lf2 = 0;                          // per lane: L and L^2 of the iterations this lane drew
+  int it_base = a.it0 - kRowLanes, draw_L = 0, draw_npmax = 0;
   double draw_lnu = 0.0;
 
-  // (L, 2 log u) of iteration `it` of the row's chain: lane s drew iteration it_base + s
-  int L_nxt = 0;
+  // (L, 2 log u) of iteration `it` of the row's chain: lane s drew iteration it_base + s.  What does
+  // not need the trajectory is done once per draw, for its 16 iterations: the wave's longest
+  // trajectory (pairs of steps, the maximum over the four rows, the same in every row), and the
+  // L and L^2 tallies of the drawn iterations this launch runs (exact integers; the rows' lanes are
+  // summed once at the end of the kernel).
+  int L_nxt = 0, np_max = 0;
   double lnu_nxt = 0.0;
   auto fetch_L = [&](int it) {
     if (it - it_base >= kRowLanes) {
@@ -203,7 +286,14 @@ __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4
       const double u = u53(rr.z, rr.w);
       draw_lnu = u > 0.0 ? fast_log(u) : -__builtin_inf();
       draw_lnu *= 2.0;                                   // compared with 2 dE (exact scaling)
+      int m = draw_L >> 1;
+      m = max(m, __builtin_amdgcn_ds_bpermute(4 * (lane ^ 16), m));
+      draw_npmax = max(m, __builtin_amdgcn_ds_bpermute(4 * (lane ^ 32), m));
+      const uint32_t Lr = it + s < a.it1 ? (uint32_t)draw_L : 0u;
+      n_lf += Lr;
+      n_lf2 += __umul24(Lr, Lr);                         // host: L_high < 2^12
     }
+    np_max = __builtin_amdgcn_readlane(draw_npmax, it - it_base);
     const int bsrc = (int)(bprow + 4u * (uint32_t)(it - it_base));
     L_nxt = __builtin_amdgcn_ds_bpermute(bsrc, draw_L);
     lnu_nxt = __hiloint2double(__builtin_amdgcn_ds_bpermute(bsrc, __double2hiint(draw_lnu)),
@@ -233,8 +323,6 @@ __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4
       q[e] = __builtin_fma(sq, t, q[e]);                 // u[1] = u[0] + dt t (odd L) or u[0]
     }
     const int np = L >> 1;                                // paired steps of this row
-    const int np_max = s_max_i32(s_max_i32(__builtin_amdgcn_readlane(np, 0), __builtin_amdgcn_readlane(np, 16)),
-                                 s_max_i32(__builtin_amdgcn_readlane(np, 32), __builtin_amdgcn_readlane(np, 48)));
     // Pairs of steps up to the wave's longest trajectory.  v_cmpx takes the rows that are done out of
     // EXEC (it only ever shrinks inside the loop: a finished row stays finished), one VALU per pair.
     if (np_max > 0) {
@@ -271,13 +359,12 @@ __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4
     for (int e = 0; e < C; ++e) w[e] = __builtin_fma(a.lf_ch, q[e], -x[e]);
     double m1l = rows_sumsq<C>(q, 0.0);
     const double k1 = __builtin_fma(rows_sumsq<C>(w, 0.0), a.lf_idt2, m1l);
-    const double s2 = row_sum_l15(k1 - e0l);             // lane 15 of the row: 2 (E1 - E0)
-    const double se = row_sum_l15(e0l);                  // lane 15 of the row: 2 E0 - logc
-    E0 = __builtin_fma(se, 0.5, hlogc);
+    // one reduction for both: lane 7 of the row holds 2 (E1 - E0), lane 15 holds 2 E0 - logc
+    const double s2 = row_sum2_l7_l15(k1 - e0l, e0l);
+    E0 = __builtin_fma(s2, 0.5, hlogc);                   // the energy: lane 15
     if (write_row) {
       if (nbuf == 0) row_first = row;
-      Ebuf = park_row_shift(Ebuf, E0);
-      dEbuf = park_row_shift(dEbuf, E0 - Eprev);
+      park_rows(Ebuf, dEbuf, E0, E0 - Eprev, lane15);
       if (++nbuf == kRowLanes) {
         flush_E(kRowLanes);
         nbuf = 0;
@@ -285,10 +372,10 @@ __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4
     }
     Eprev = E0;
     if (it + 1 < a.it1) ring_momentum(it + 1);           // p (x) is dead: the next momentum goes into it
-    // the test in lane 15 of each row; the four bits widened to row masks on the SALU
-    const uint64_t b15 = (__builtin_amdgcn_ballot_w64(s2 < 0.0) | __builtin_amdgcn_ballot_w64(lnu < -s2)) &
-                         0x8000800080008000ull;
-    const uint64_t accm = (b15 << 1) - (b15 >> 15);
+    // the test in lane 7 of each row (where the reduction leaves 2 dE; lnu is the same in the row's
+    // lanes); the four bits widened to row masks on the SALU
+    const uint64_t b7 = (__builtin_amdgcn_ballot_w64(s2 < 0.0) | __builtin_amdgcn_ballot_w64(lnu < -s2)) & kRowLane7;
+    const uint64_t accm = (b7 << 9) - (b7 >> 7);
     const uint64_t rej = ~accm;
     if (rej != 0) {                                       // uniform; restores the rejecting rows under EXEC
       uint64_t ex;
@@ -317,9 +404,8 @@ __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4
           __builtin_nontemporal_store(q[j], reinterpret_cast<double*>(rowb + qoff) + kRowLanes * j);
     }
     if (post) add_mask(n_acc, accm); else add_mask(n_acc_wu, accm);
-    add_mask(n_oob, it < a.i_oob ? rej : 0ull);
-    n_lf += (uint32_t)L;
-    n_lf2 += __umul24((uint32_t)L, (uint32_t)L);    // host: L_high < 2^12
+    // a rejection before i_oob = wu - Lc thin <= wu: only the warm-up instance can meet one
+    if constexpr (!post) add_mask(n_oob, it < a.i_oob ? rej : 0ull);
     e0l = rows_sumsq<C>(p, m0l);
     if (post && ++phase == a.thin) {
       phase = 0;
@@ -335,7 +421,9 @@ __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4
 #pragma unroll
   for (int j = 0; j < C; ++j)
     if (j < C - 1 ? valid : st6) qst[kRowLanes * j] = q[j];
-  if (valid && s == kRowLanes - 1) {                      // lane 15: where the row sums leave E
+  n_lf = row_sum_u32_l15(n_lf);
+  n_lf2 = row_sum_u32_l15(n_lf2);
+  if (valid && s == kRowLanes - 1) {                      // lane 15: where the row sums leave E and the tallies
     a.Eprev[c] = Eprev;
     if (a.cnt) {
       unsigned long long* cs = a.cnt + (c & (HMC_COUNTER_SLOTS - 1)) * HMC_NCOUNTERS;
@@ -356,6 +444,10 @@ hipError_t launch_rows_iters(const RandArgs& a, hipStream_t s) {
   int dev = 0;
   if (hipError_t e = hipGetDevice(&dev)) return e;
   if (dev < 0 || dev >= 64 || !raised[dev]) {
+    // the kernel addresses its dynamic LDS from byte 0: it must have no static LDS in front of it
+    hipFuncAttributes fa;
+    if (hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&k_rows_iters<7>))) return e;
+    if (fa.sharedSizeBytes != 0) return hipErrorInvalidConfiguration;
     if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rows_iters<7>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRowsLds))
       return e;
