@@ -548,6 +548,60 @@ int32_t hmc_glm_predictive_blocks(int32_t D, int64_t n_eval, int64_t n_samples);
 hmc_status hmc_glm_predictive(const hmc_glm* eval, const hmc_samples* s, double* out, void* workspace,
                               int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------- order statistics (quantiles)
+ * Exact order statistics of every dimension of a strided sample view (hmc_samples above), on the
+ * device, without copying or sorting the samples: the k-th smallest of the M = n_chains x
+ * rows-per-chain values of dimension d, for up to HMC_SELECT_MAX_RANKS ranks k per call, shared by
+ * all D dimensions.  out[T][D]; out[t][d] equals np.sort(x[:, d])[ranks[t]] bit for bit, except
+ * that a zero may come back with either sign.  NaNs of either sign sort last, as NumPy sorts them,
+ * and come back as the canonical quiet NaN.  Quantiles and credible intervals are interpolated on
+ * the host from two order statistics each (hmc_amd.quantiles).
+ * Method (hmc_select.hip): radix select, most significant digit first, HMC_SELECT_BITS bits per
+ *   pass, 64 / HMC_SELECT_BITS passes, over the order-preserving key of a double: every bit of a
+ *   negative value flipped, the sign bit of a non-negative one; every NaN is the largest key
+ *   (csrc/hmc_select.hpp states the map, its inverse and the pick rule once).  A pass has two steps:
+ *     count  reads the view once; counts[D][T][2^BITS] (int64) receives, for every (dimension, rank),
+ *            the elements whose key starts with that target's prefix, binned by their next digit.
+ *            Blocks count in 32-bit LDS histograms and add them with integer atomics.  Ranks that
+ *            still share a prefix share bins: only the lowest of them (its owner) is counted.
+ *     pick   per (dimension, rank): the digit whose bin holds the remaining rank is appended to the
+ *            prefix, and the bins below it are subtracted from the remaining rank.
+ *   Only integers are added, so the result is a function of each dimension's multiset of values
+ *   alone: no bit depends on the launch geometry, the device, or how chains are split over shards.
+ *   Shards (ranks of a multi-GPU run) call count on their own chains with the same state, sum their
+ *   counts tables (an all-reduce) and call pick on the sum: additive over shards.
+ * state: HMC_SELECT_STATE_STRIDE int64 words per (dimension, rank), [D][T]:
+ *   0 prefix (the key's top BITS x pass bits, right-aligned)   1 remaining rank   2 owner
+ *   3 padding to a 32-byte record (no record straddles a 64-byte line), written 0 by hmc_select_init
+ * hmc_select_workspace_size(D, T): bytes of state followed by counts, as hmc_order_stats lays them
+ *   out (0 for D < 1 or T outside 1 .. HMC_SELECT_MAX_RANKS).  hmc_select_grid(D, n_samples): the
+ *   blocks per tile of 16 dimensions that count launches, a function of the two alone (0: no launch).
+ * hmc_select_init    state for `ranks` (host int64[T]), each in [0, n_samples), n_samples = M over
+ *                    all shards
+ * hmc_select_count   zeroes counts, then counts this view's samples for pass = 0 .. 64/BITS - 1
+ * hmc_select_pick    advances state by one pass from counts
+ * hmc_select_values  out[T][D] from state after the last pass
+ * hmc_order_stats    all of it on one device, with no host synchronisation in between; workspace of
+ *                    hmc_select_workspace_size bytes
+ * HMC_EINVAL: a NULL s, ranks, state, counts, out or workspace; a NULL q with M > 0; D < 1; T outside
+ *   1 .. HMC_SELECT_MAX_RANKS; a rank outside [0, M); row_stride < D; row_step < 1; row_begin < 0,
+ *   row_end < row_begin or n_chains < 0; pass outside 0 .. 64/BITS - 1; workspace_bytes below the
+ *   size query.  HMC_ENOTSUP: D > 16 x 65535, M > 2^48.  All checks run on the host before any
+ *   launch.  M == 0: HMC_OK, nothing is launched and out is untouched; q may then be NULL (an empty
+ *   shard has no storage), and hmc_select_count still zeroes counts, the shard's share of the sum. */
+enum { HMC_SELECT_BITS = 8, HMC_SELECT_MAX_RANKS = 8, HMC_SELECT_STATE_STRIDE = 4 };
+
+int64_t hmc_select_workspace_size(int32_t D, int32_t T);
+int64_t hmc_select_grid(int32_t D, int64_t n_samples);
+hmc_status hmc_select_init(int64_t* state, int32_t D, int32_t T, const int64_t* ranks, int64_t n_samples,
+                           void* stream);
+hmc_status hmc_select_count(const hmc_samples* s, int32_t D, int32_t T, int32_t pass, const int64_t* state,
+                            int64_t* counts, void* stream);
+hmc_status hmc_select_pick(int32_t D, int32_t T, int32_t pass, int64_t* state, const int64_t* counts, void* stream);
+hmc_status hmc_select_values(int32_t D, int32_t T, const int64_t* state, double* out, void* stream);
+hmc_status hmc_order_stats(const hmc_samples* s, int32_t D, int32_t T, const int64_t* ranks, double* out,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+
 /* The standard normals the Philox mode draws for (chain, iteration): out[n][2*npairs].
  * Debug/verification entry (statistical tests of the in-kernel generator). */
 hmc_status hmc_rng_normals(uint64_t seed, int64_t chain0, int64_t n, int32_t iteration,

@@ -16,6 +16,7 @@
 #include "hmc_logit.hpp"
 #include "hmc_mix.hpp"
 #include "hmc_pred.hpp"
+#include "hmc_select.hpp"
 
 namespace {
 
@@ -1003,6 +1004,136 @@ hmc_status hmc_glm_predictive(const hmc_glm* eval, const hmc_samples* s, double*
                 "(hmc_glm_predictive_workspace_size)", what, (long long)workspace_bytes, eval->D, eval->n,
                 (long long)n_samples, (long long)need);
   return hip_status(hmc::launch_pred(*eval, *s, rows, n_samples, out, (double*)workspace, (hipStream_t)stream), what);
+}
+
+// ---------------------------------------------------------------- order statistics (radix select)
+namespace {
+
+// The view's own checks; *rows and *n_samples on success.
+hmc_status select_view(const hmc_samples* s, int32_t D, const char* what, int64_t* rows, int64_t* n_samples) {
+  if (!s) return fail(HMC_EINVAL, "%s: null sample set", what);
+  if (D < 1) return fail(HMC_EINVAL, "%s: D must be >= 1", what);
+  if (s->row_stride < D) return fail(HMC_EINVAL, "%s: row_stride=%lld < D=%d", what, (long long)s->row_stride, D);
+  if (s->row_step < 1) return fail(HMC_EINVAL, "%s: row_step=%lld must be >= 1", what, (long long)s->row_step);
+  if (s->row_begin < 0 || s->row_end < s->row_begin || s->n_chains < 0)
+    return fail(HMC_EINVAL, "%s: rows [%lld, %lld) of %lld chains", what, (long long)s->row_begin,
+                (long long)s->row_end, (long long)s->n_chains);
+  *rows = (s->row_end - s->row_begin + s->row_step - 1) / s->row_step;
+  if (*rows > 0 && s->n_chains > INT64_MAX / *rows) return fail(HMC_EINVAL, "%s: chains x rows overflows", what);
+  *n_samples = s->n_chains * *rows;
+  if (*n_samples > 0 && !s->q) return fail(HMC_EINVAL, "%s: null q", what);   // an empty view has no storage
+  return HMC_OK;
+}
+
+hmc_status select_shape(int32_t D, int32_t T, const char* what) {
+  if (D < 1) return fail(HMC_EINVAL, "%s: D must be >= 1", what);
+  if (T < 1 || T > HMC_SELECT_MAX_RANKS)
+    return fail(HMC_EINVAL, "%s: T=%d ranks, a call takes 1 .. %d", what, T, HMC_SELECT_MAX_RANKS);
+  if (hmc::select_tiles(D) > hmc::kSelMaxTiles)
+    return fail(HMC_ENOTSUP, "%s: D=%d, the kernel takes D <= %lld", what, D,
+                (long long)(hmc::kSelMaxTiles * hmc::kSelTile));
+  return HMC_OK;
+}
+
+hmc_status select_pass(int32_t pass, const char* what) {
+  if (pass < 0 || pass >= hmc::kSelPasses)
+    return fail(HMC_EINVAL, "%s: pass=%d outside 0 .. %d", what, pass, hmc::kSelPasses - 1);
+  return HMC_OK;
+}
+
+hmc_status select_ranks(const int64_t* ranks, int32_t T, int64_t n_samples, const char* what, hmc::SelectRanks* out) {
+  if (!ranks) return fail(HMC_EINVAL, "%s: null ranks", what);
+  for (int t = 0; t < HMC_SELECT_MAX_RANKS; ++t) out->r[t] = 0;
+  for (int t = 0; t < T; ++t) {
+    if (ranks[t] < 0 || ranks[t] >= n_samples)
+      return fail(HMC_EINVAL, "%s: rank %lld outside [0, %lld)", what, (long long)ranks[t], (long long)n_samples);
+    out->r[t] = ranks[t];
+  }
+  return HMC_OK;
+}
+
+}  // namespace
+
+int64_t hmc_select_workspace_size(int32_t D, int32_t T) {
+  if (D < 1 || T < 1 || T > HMC_SELECT_MAX_RANKS) return 0;
+  return (hmc::select_state_words(D, T) + hmc::select_count_words(D, T)) * (int64_t)sizeof(int64_t);
+}
+
+int64_t hmc_select_grid(int32_t D, int64_t n_samples) { return hmc::select_blocks(D, n_samples); }
+
+hmc_status hmc_select_init(int64_t* state, int32_t D, int32_t T, const int64_t* ranks, int64_t n_samples,
+                           void* stream) {
+  const char* what = "hmc_select_init";
+  if (hmc_status e = select_shape(D, T, what)) return e;
+  if (n_samples < 0) return fail(HMC_EINVAL, "%s: n_samples < 0", what);
+  if (n_samples == 0) return HMC_OK;
+  hmc::SelectRanks r;
+  if (hmc_status e = select_ranks(ranks, T, n_samples, what, &r)) return e;
+  if (!state) return fail(HMC_EINVAL, "%s: null state", what);
+  return hip_status(hmc::launch_select_init(state, D, T, r, (hipStream_t)stream), what);
+}
+
+hmc_status hmc_select_count(const hmc_samples* s, int32_t D, int32_t T, int32_t pass, const int64_t* state,
+                            int64_t* counts, void* stream) {
+  const char* what = "hmc_select_count";
+  if (hmc_status e = select_shape(D, T, what)) return e;
+  if (hmc_status e = select_pass(pass, what)) return e;
+  int64_t rows = 0, n_samples = 0;
+  if (hmc_status e = select_view(s, D, what, &rows, &n_samples)) return e;
+  if (!state || !counts) return fail(HMC_EINVAL, "%s: null state or counts", what);
+  if (n_samples > 0 && hmc::select_blocks(D, n_samples) == 0)
+    return fail(HMC_ENOTSUP, "%s: D=%d with %lld samples is past the launch's limits (2^48 samples, 2^31 blocks)",
+                what, D, (long long)n_samples);
+  // an empty shard still contributes a table of zeros to the sum over shards
+  if (n_samples == 0) return hip_status(hmc::zero_select_counts(counts, D, T, (hipStream_t)stream), what);
+  return hip_status(hmc::launch_select_count(*s, rows, n_samples, D, T, pass, state, counts, (hipStream_t)stream),
+                    what);
+}
+
+hmc_status hmc_select_pick(int32_t D, int32_t T, int32_t pass, int64_t* state, const int64_t* counts, void* stream) {
+  const char* what = "hmc_select_pick";
+  if (hmc_status e = select_shape(D, T, what)) return e;
+  if (hmc_status e = select_pass(pass, what)) return e;
+  if (!state || !counts) return fail(HMC_EINVAL, "%s: null state or counts", what);
+  return hip_status(hmc::launch_select_pick(D, T, state, counts, (hipStream_t)stream), what);
+}
+
+hmc_status hmc_select_values(int32_t D, int32_t T, const int64_t* state, double* out, void* stream) {
+  const char* what = "hmc_select_values";
+  if (hmc_status e = select_shape(D, T, what)) return e;
+  if (!state || !out) return fail(HMC_EINVAL, "%s: null state or out", what);
+  return hip_status(hmc::launch_select_values(D, T, state, out, (hipStream_t)stream), what);
+}
+
+hmc_status hmc_order_stats(const hmc_samples* s, int32_t D, int32_t T, const int64_t* ranks, double* out,
+                           void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* what = "hmc_order_stats";
+  if (hmc_status e = select_shape(D, T, what)) return e;
+  int64_t rows = 0, n_samples = 0;
+  if (hmc_status e = select_view(s, D, what, &rows, &n_samples)) return e;
+  if (!ranks) return fail(HMC_EINVAL, "%s: null ranks", what);
+  if (n_samples == 0) return HMC_OK;                     // no order statistic exists: out stays as it is
+  if (n_samples > 0 && hmc::select_blocks(D, n_samples) == 0)
+    return fail(HMC_ENOTSUP, "%s: D=%d with %lld samples is past the launch's limits (2^48 samples, 2^31 blocks)",
+                what, D, (long long)n_samples);
+  hmc::SelectRanks r;
+  if (hmc_status e = select_ranks(ranks, T, n_samples, what, &r)) return e;
+  if (!out) return fail(HMC_EINVAL, "%s: null out", what);
+  const int64_t need = hmc_select_workspace_size(D, T);
+  if (!workspace) return fail(HMC_EINVAL, "%s: null workspace", what);
+  if (workspace_bytes < need)
+    return fail(HMC_EINVAL, "%s: workspace of %lld bytes, D=%d with %d ranks needs %lld (hmc_select_workspace_size)",
+                what, (long long)workspace_bytes, D, T, (long long)need);
+  int64_t* state = (int64_t*)workspace;
+  int64_t* counts = state + hmc::select_state_words(D, T);
+  hipStream_t st = (hipStream_t)stream;
+  if (hmc_status e = hip_status(hmc::launch_select_init(state, D, T, r, st), what)) return e;
+  for (int pass = 0; pass < hmc::kSelPasses; ++pass) {
+    if (hmc_status e = hip_status(hmc::launch_select_count(*s, rows, n_samples, D, T, pass, state, counts, st), what))
+      return e;
+    if (hmc_status e = hip_status(hmc::launch_select_pick(D, T, state, counts, st), what)) return e;
+  }
+  return hip_status(hmc::launch_select_values(D, T, state, out, st), what);
 }
 
 hmc_status hmc_rng_normals(uint64_t seed, int64_t chain0, int64_t n, int32_t iteration, int32_t npairs, double* out,

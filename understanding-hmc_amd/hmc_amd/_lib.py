@@ -94,6 +94,11 @@ class Samples(ctypes.Structure):
                 ("row_step", ctypes.c_int64)]
 
 
+# include/hmc.h HMC_SELECT_BITS, HMC_SELECT_MAX_RANKS, HMC_SELECT_STATE_STRIDE (radix select)
+SELECT_BITS, SELECT_MAX_RANKS, SELECT_STATE_STRIDE = 8, 8, 4
+SELECT_BINS, SELECT_PASSES = 1 << SELECT_BITS, 64 // SELECT_BITS
+
+
 # Exported symbols (tests check every one of these is present; keep in sync with include/hmc.h)
 SYMBOLS = {
     "hmc_version": (ctypes.c_char_p, []),
@@ -175,6 +180,16 @@ SYMBOLS = {
     "hmc_glm_predictive_blocks": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int64, ctypes.c_int64]),
     "hmc_glm_predictive": (ctypes.c_int, [ctypes.POINTER(GLM), ctypes.POINTER(Samples), c_dp, c_dp, ctypes.c_int64,
                                           c_dp]),
+    "hmc_select_workspace_size": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32]),
+    "hmc_select_grid": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int64]),
+    "hmc_select_init": (ctypes.c_int, [c_dp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_int64),
+                                       ctypes.c_int64, c_dp]),
+    "hmc_select_count": (ctypes.c_int, [ctypes.POINTER(Samples), ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                        c_dp, c_dp, c_dp]),
+    "hmc_select_pick": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, c_dp, c_dp, c_dp]),
+    "hmc_select_values": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, c_dp, c_dp, c_dp]),
+    "hmc_order_stats": (ctypes.c_int, [ctypes.POINTER(Samples), ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.POINTER(ctypes.c_int64), c_dp, c_dp, ctypes.c_int64, c_dp]),
     "hmc_rng_normals": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32,
                                        ctypes.c_int32, c_dp, c_dp]),
     "hmc_philox": (ctypes.c_int, [ctypes.c_uint32] * 6 + [ctypes.c_int64, c_dp, c_dp]),

@@ -420,6 +420,32 @@ class HMC_sampler(sampler):
         part = self._predictive_partials(getattr(t, "X", None), getattr(t, "y", None), "waic")
         return P.finish(part, t.y, t.family)
 
+    # ------------------------------------------------------------------ posterior quantiles
+    def _stored_samples(self, what):
+        """The stored samples of the last run: q_chain_device where the run left it, else q_chain
+        (the source rule of _predictive_partials)."""
+        src = getattr(self, "q_chain_device", None)
+        if src is None and getattr(self, "engine", None) is not None:
+            src = self.q_chain
+        if src is None:
+            raise RuntimeError("%s needs the samples of a run: call gen_sample first (with store_chain)" % what)
+        return src
+
+    def quantiles(self, probs=(0.05, 0.5, 0.95)):
+        """Posterior quantiles of every coordinate over rows 1.. of every chain (the start row is
+        dropped, as compute_convergence_stats does): a (len(probs), D) array equal to
+        np.quantile(q_chain[:, 1:].reshape(-1, D), probs, axis=0), from exact order statistics selected
+        on the device (hmc_amd.quantiles).  Any target, either sampler; after gen_sample."""
+        from . import quantiles as Q
+        return Q.quantiles(self._stored_samples("quantiles"), probs, rows=slice(1, None), device=self.device)
+
+    def credible_interval(self, level=0.9):
+        """The central credible interval of every coordinate: the (lo, hi) pair of (D,) arrays of the
+        posterior quantiles (1 - level) / 2 and 1 - (1 - level) / 2 (hmc_amd.quantiles)."""
+        from . import quantiles as Q
+        return Q.credible_interval(self._stored_samples("credible_interval"), level, rows=slice(1, None),
+                                   device=self.device)
+
     def _finish(self, eng, elapsed, verbose):
         """Copy results to the reference's NumPy attributes and derive the counters."""
         c = eng.read_counters()
