@@ -222,16 +222,20 @@ __device__ __forceinline__ void normal_pair(uint4 r, double& z0, double& z1) {
 // ---- table-driven Box–Muller (the wave kernel's momentum draws).  Per block, two small LDS
 // tables built once with the ~1-ulp kernels above:
 //   trig[i] = (cos, sin)(2*pi*i/1024), i < 1024          (16 KB)
-//   logt[j] = (1/c_j, -log(1/c_j)), c_j = centre of the j-th of 1024 buckets of [0.5, 1)
-//             (the last bucket uses c = 1: log is then log1p(m - 1), relative-accurate near 1)
+//   logt[j] = (-2/c_j, 2 log(1/c_j)), c_j = centre of the j-th of 1024 buckets of [0.5, 1)
+//             (the last bucket uses c = 1: log is then log1p(m - 1), relative-accurate near 1);
+//             the entries carry the radius's factor -2 (hmc_bm_radius.hpp)
 // so that log and sincos reduce to short Horner chains around a table point (1024 entries: two
 // fewer terms in each series than 256/128 entries, for 16 KB more LDS per block).
+}  // namespace hmc
+#include "hmc_bm_radius.hpp"   // kLogN, kLogShift, the log table's entries and -2 log(u1) from them
+namespace hmc {
 #ifdef HMC_SMALL_TABLES
-constexpr int kTrigN = 256, kLogN = 128;
+constexpr int kTrigN = 256;
 #else
-constexpr int kTrigN = 1024, kLogN = 1024;
+constexpr int kTrigN = 1024;
 #endif
-constexpr int kLogShift = kLogN == 1024 ? 10 : 13, kTrigShift = kTrigN == 1024 ? 10 : 12;
+constexpr int kTrigShift = kTrigN == 1024 ? 10 : 12;
 constexpr int kNormalTableDoubles = 2 * kTrigN + 2 * kLogN;
 
 // Every thread of the block calls this, then the block synchronises.
@@ -245,38 +249,13 @@ __device__ __forceinline__ void init_normal_tables(double* tab) {
   for (int j = threadIdx.x; j < kLogN; j += blockDim.x) {
     const double c = j == kLogN - 1 ? 1.0 : 0.5 + ((double)j + 0.5) * (0.5 / kLogN);
     const double ic = j == kLogN - 1 ? 1.0 : rcp_nr(c);
-    tab[2 * kTrigN + 2 * j] = ic;
-    tab[2 * kTrigN + 2 * j + 1] = j == kLogN - 1 ? 0.0 : -fast_log(ic);
+    const bm_entry e = bm_log_entry(ic, j == kLogN - 1 ? 0.0 : -fast_log(ic));
+    tab[2 * kTrigN + 2 * j] = e.x;
+    tab[2 * kTrigN + 2 * j + 1] = e.y;
   }
 }
 
 __device__ __forceinline__ double2 lds_pair(const double* p) { return *reinterpret_cast<const double2*>(p); }
-
-// log(u) for u in (0, 1] from the tables: u = 2^k m, m in [0.5, 1); bucket j = top 10 mantissa
-// bits; log m = L_j + log1p(m / c_j - 1) with |r| <= 2^-11 (series to r^5; r^6/6 < 2^-68).
-__device__ __forceinline__ double table_log(double u, const double* tab) {
-  const int k = __builtin_amdgcn_frexp_exp(u);
-  const double m = __builtin_amdgcn_frexp_mant(u);
-  const uint32_t mhi = (uint32_t)(__builtin_bit_cast(uint64_t, m) >> 32);
-  // byte offset 16 j of bucket j = (mhi >> kLogShift) & (kLogN - 1): one shift, one and
-  const uint32_t j16 = (mhi >> (kLogShift - 4)) & ((kLogN - 1) << 4);
-  const double2 e = lds_pair(reinterpret_cast<const double*>(reinterpret_cast<const char*>(tab + 2 * kTrigN) + j16));
-  const double r = __builtin_fma(m, e.x, -1.0);
-#ifdef HMC_SMALL_TABLES
-  double pl = fmac_k(r, 1.0 / 7.0, -1.0 / 6.0);
-  pl = fmac_k(r, pl, 1.0 / 5.0);
-  pl = fmac_k(r, pl, -1.0 / 4.0);
-#else
-  // (an output-modifier form, (0.4 r - 0.5) with div:2, measured wrong on gfx950: omod is not
-  // applied to this f64 FMA; test_table_normals_match_kernel caught it)
-  double pl = fmac_k(r, 1.0 / 5.0, -1.0 / 4.0);
-#endif
-  pl = fmac_k(r, pl, 1.0 / 3.0);
-  pl = __builtin_fma(r, pl, -0.5);                                      // inline constant
-  const double l1p = __builtin_fma(r * r, pl, r);                       // log1p(r)
-  const double dk = (double)k;
-  return __builtin_fma(dk, 6.93147180369123816490e-01, e.y + __builtin_fma(dk, 1.90821492927058770002e-10, l1p));
-}
 
 // (cos, sin)(2*pi*(d - 1)) for d in [1, 2) holding 52 random mantissa bits: table point from the
 // top 10 bits, the rest delta in [0, 2*pi/1024) by Taylor series (sin to delta^5, cos to delta^6:
@@ -312,7 +291,7 @@ __device__ __forceinline__ void table_cossin(double d, const double* tab, double
 
 // Two independent N(0,1) from one Philox block, table-driven Box–Muller (same uniforms as
 // normal_pair: u1 = 2 - d1 in (0, 1], angle 2*pi*(d2 - 1)).
-// sqrt(t) for the Box-Muller radius: t = -2 log u1 >= 0 up to the table log's rounding at u1 = 1
+// sqrt(t) for the Box-Muller radius: t = -2 log u1 (bm_neg2_log) >= 0 up to its rounding at u1 = 1
 // (probability 2^-52), so one v_max against a tiny floor replaces fast_sqrt's zero test and its
 // two selects (radius 2^-500 instead of 0 there).
 __device__ __forceinline__ double bm_sqrt(double t) {
@@ -328,7 +307,7 @@ __device__ __forceinline__ double bm_sqrt(double t) {
 
 __device__ __forceinline__ void normal_pair_tab(uint4 r, const double* tab, double& z0, double& z1) {
   const double u1 = 2.0 - one_to_two(r.x, r.y);
-  const double rad = bm_sqrt(-2.0 * table_log(u1, tab));
+  const double rad = bm_sqrt(bm_neg2_log(u1, tab + 2 * kTrigN));
   double c, s;
   table_cossin(one_to_two(r.z, r.w), tab, c, s);
   z0 = rad * c;

@@ -399,10 +399,12 @@ bool rows_shape(int D, int L_low, int L_high) {
 
 // ... and the launches it takes: those of the production wave instance (FAST, identity target and
 // mass, three-term leapfrog, Philox, no chain-0 capture or debug hooks), with a sample window whose
-// rows of the wave's four chains lie within a 32-bit byte offset of the first.
+// rows of the wave's four chains lie within a 32-bit byte offset of the first, and so do their rows
+// of the energy chains.
 bool rows_kernel(const RandArgs& a, const Layout& lay, bool exact, bool gen, bool replay) {
   const bool full = a.traj_q != nullptr || a.dbg != 0 || a.dbgL >= 0;
   if (replay || full || !rows_shape(a.D, a.L_low, a.L_high) || !leapfrog_three_term(a, lay, exact, gen)) return false;
+  if ((a.Ec || a.dEc) && 4 * (int64_t)a.Lc * 8 >= (int64_t)1 << 31) return false;
   return !a.qc || 4 * (int64_t)a.Lq * a.D * 8 < (int64_t)1 << 31;
 }
 

@@ -13,6 +13,9 @@
 //     through EXEC;
 //   * the energy lands in lane 15 of each row and the decision is formed in lane 7; its four bits
 //     are widened to row masks on the SALU, and a reject restores under that EXEC mask;
+//   * the state lives in one of two register sets and the trajectory is integrated into the other, so
+//     the set it started from is the restore point and nothing is copied per iteration; the next
+//     iteration swaps the two roles (the loop body stands twice per trip, role as a template constant);
 //   * momentum: every pass draws 16 consecutive pairs of each row's own (pair, iteration) stream
 //     into that chain's LDS ring (stream order, ten 128-B chunks; the first is mirrored behind the
 //     tenth, so that a read which starts in the last chunk runs on without a per-lane wrap).  The
@@ -177,7 +180,7 @@ __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4
   int rbaseb = 0;                                         // ring position (bytes) of the next iteration's doubles
   const int dpb = 16 * a.npairs;                          // stream bytes per iteration
   const uint32_t rlane = ringrow + 8 * s;
-  double q[C], p[C], qi[C];
+  double q[C], qt[C], p[C];                             // the two state sets (roles swap per iteration) and the momentum
   // 16 pairs on: gkb += 256, and past the iteration's last pair gkb -= 16 npairs, git += 1 (four VALU:
   // the borrow of gkb - 16 npairs picks both)
   auto advance = [&](uint32_t& k, uint32_t& i) {
@@ -222,28 +225,36 @@ __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4
     for (int j = 0; j < C; ++j) {
       uint32_t cj = cbb + kRowChunkBytes * j;
       if (cj >= kRowRingBytes) cj -= kRowRingBytes;
-      p[j] = *lds_at<double>(kRowRingOff + (opaque_s32(cj) + a0));
+      // The last slot is read under EXEC by the lanes that own a coordinate in it.  The others keep the
+      // zero the slot was given before the loop: a zero coordinate with a zero momentum stays an exact
+      // zero through every leapfrog step (p's registers hold x between two draws), so no select follows
+      // the read.  (st6, not v6: what a row past the last chain holds there is never stored, and one
+      // mask less stays in SGPRs through the loop.)
+      if (j < C - 1 || st6) p[j] = *lds_at<double>(kRowRingOff + (opaque_s32(cj) + a0));
     }
-    p[C - 1] = v6 ? p[C - 1] : 0.0;                       // dimension past D: no such coordinate
     rbaseb += dpb;
     if (rbaseb >= (int)kRowRingBytes) rbaseb -= kRowRingBytes;
   };
 
-  double* const qst = a.q + c * (int64_t)a.D + s;
+  // the state: wave-uniform base (chain c0) + this lane's 32-bit byte offset, as every address below
+  // (a 64-bit address per lane kept to the end of the kernel costs two VGPRs each)
+  char* const qstb = reinterpret_cast<char*>(a.q + c0 * (int64_t)a.D);
+  const uint32_t qstoff = (uint32_t)(r * a.D + s) * 8u;
 #pragma unroll
   for (int j = 0; j < C; ++j) {
     q[j] = 0.0;
-    if (j < C - 1 ? valid : st6) q[j] = qst[kRowLanes * j];
+    if (j < C - 1 ? valid : st6) q[j] = reinterpret_cast<const double*>(qstb + qstoff)[kRowLanes * j];
   }
-  double Eprev = valid ? a.Eprev[c] : 0.0;
+  double Eprev = valid ? reinterpret_cast<const double*>(reinterpret_cast<char*>(a.Eprev + c0) + 8u * r)[0] : 0.0;
   __builtin_amdgcn_s_waitcnt(0x0F70);                    // retire state loads before the loop (vmcnt(0))
 
+  p[C - 1] = 0.0;                                        // dimension past D: no such coordinate
   ring_momentum(a.it0);
   const double hlogc = 0.5 * a.logc;
   const uint64_t lane15 = kRowLane15;
-  double m0l = rows_sumsq<C>(q, 0.0);                    // this lane's part of q.q
-  double e0l = rows_sumsq<C>(p, m0l);                    // ... and of q.q + p.p at the iteration start
-  double E0 = 0.0;
+  double ml = rows_sumsq<C>(q, 0.0), mtl = 0.0;          // this lane's part of q.q, of either state set
+  double e0l = rows_sumsq<C>(p, ml);                     // ... and of q.q + p.p at the iteration start
+  double Et = 0.0;                                       // the energy of an iteration: Eprev and Et swap roles too
 
   int row = 0, phase = 0;
   if (a.it0 >= a.wu) {
@@ -254,16 +265,18 @@ __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4
   double Ebuf = 0.0, dEbuf = 0.0;
   int row_first = 0, nbuf = 0;
   const uint32_t bprow = (uint32_t)(lane & ~(kRowLanes - 1)) * 4;
-  double* const Ec = a.Ec ? a.Ec + c * (int64_t)a.Lc + s : nullptr;
-  double* const dEc = a.dEc ? a.dEc + c * (int64_t)a.Lc + s : nullptr;
+  char* const Ecb = a.Ec ? reinterpret_cast<char*>(a.Ec + c0 * (int64_t)a.Lc) : nullptr;
+  char* const dEcb = a.dEc ? reinterpret_cast<char*>(a.dEc + c0 * (int64_t)a.Lc) : nullptr;
+  const uint32_t eoff = (uint32_t)(r * a.Lc + s) * 8u;         // host: 3 Lc 8 + 128 < 2^31
   // sample rows: wave-uniform base (chain c0, row qslot) + this lane's 32-bit byte offset
   char* const qcb = a.qc ? reinterpret_cast<char*>(a.qc + c0 * (int64_t)a.Lq * a.D) : nullptr;
   const uint32_t qoff = (uint32_t)(r * a.Lq * a.D + s) * 8u;   // host: 3 Lq D 8 + 1 KB < 2^31
   auto flush_E = [&](int n) {          // rows row_first .. row_first + n - 1 from lanes 0 .. n-1 of each row
     const int first = kRowLanes - n;   // the n parked values sit in lanes 16 - n .. 15, oldest first
     if (valid && s >= first) {
-      if (Ec) __builtin_nontemporal_store(Ebuf, Ec + (row_first - first));
-      if (dEc) __builtin_nontemporal_store(dEbuf, dEc + (row_first - first));
+      const int64_t rowb = (int64_t)(row_first - first) * 8;
+      if (Ecb) __builtin_nontemporal_store(Ebuf, reinterpret_cast<double*>(Ecb + rowb + eoff));
+      if (dEcb) __builtin_nontemporal_store(dEbuf, reinterpret_cast<double*>(dEcb + rowb + eoff));
     }
   };
   uint32_t n_acc = 0, n_acc_wu = 0, n_oob = 0;           // per lane, the same in a row's lanes
@@ -300,14 +313,22 @@ __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4
                                __builtin_amdgcn_ds_bpermute(bsrc, __double2loint(draw_lnu)));
   };
 
-  auto iteration = [&](auto post_c, int it) {
+  // One iteration from the state in set `a` (role 0: q, role 1: qt) into set `b`, the other one.  `a`
+  // is not written: it is the restore point of a rejecting row.  ma / mb are the sets' parts of q.q,
+  // Ea the energy of the iteration before and Eb this one's.
+  auto iteration = [&](auto post_c, auto role_c, int it) __attribute__((always_inline)) {
     constexpr bool post = decltype(post_c)::value;
+    constexpr bool role = decltype(role_c)::value;
+    double (&qa)[C] = role ? qt : q;
+    double (&qb)[C] = role ? q : qt;
+    double& ma = role ? mtl : ml;
+    double& mb = role ? ml : mtl;
+    double& Ea = role ? Et : Eprev;
+    double& Eb = role ? Eprev : Et;
     const bool write_row = post && ((it == a.niter) || (phase == a.thin - 1));
     fetch_L(it);
     const int L = L_nxt;                                  // >= 1 (host)
     const double lnu = lnu_nxt;
-#pragma unroll
-    for (int e = 0; e < C; ++e) asm("v_mov_b64 %0, %1" : "=v"(qi[e]) : "v"(q[e]));
     // three-term leapfrog as in hmc_wave.hip; the parity selects are per lane (per row)
     double (&x)[C] = p;
     const uint32_t oddm = (uint32_t)__builtin_amdgcn_sbfe(L, 0, 1);   // all ones where L is odd
@@ -318,9 +339,9 @@ __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4
 #pragma unroll
     for (int e = 0; e < C; ++e) {
       double t;
-      asm("v_fma_f64 %0, %1, %2, %3" : "=v"(t) : "v"(sh), "v"(q[e]), "v"(p[e]));
-      x[e] = __builtin_fma(-sx, t, q[e]);                // u[0] (odd L) or u[-1] = u[0] - dt t
-      q[e] = __builtin_fma(sq, t, q[e]);                 // u[1] = u[0] + dt t (odd L) or u[0]
+      asm("v_fma_f64 %0, %1, %2, %3" : "=v"(t) : "v"(sh), "v"(qa[e]), "v"(p[e]));
+      x[e] = __builtin_fma(-sx, t, qa[e]);               // u[0] (odd L) or u[-1] = u[0] - dt t
+      qb[e] = __builtin_fma(sq, t, qa[e]);               // u[1] = u[0] + dt t (odd L) or u[0]
     }
     const int np = L >> 1;                                // paired steps of this row
     // Pairs of steps up to the wave's longest trajectory.  v_cmpx takes the rows that are done out of
@@ -349,35 +370,35 @@ __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4
                    "s_cbranch_scc1 1b\n\t"
                    "s_mov_b64 exec, -1"
                    : [x0] "+v"(x[0]), [x1] "+v"(x[1]), [x2] "+v"(x[2]), [x3] "+v"(x[3]), [x4] "+v"(x[4]),
-                     [x5] "+v"(x[5]), [x6] "+v"(x[6]), [q0] "+v"(q[0]), [q1] "+v"(q[1]), [q2] "+v"(q[2]),
-                     [q3] "+v"(q[3]), [q4] "+v"(q[4]), [q5] "+v"(q[5]), [q6] "+v"(q[6]), [i] "=&s"(i)
+                     [x5] "+v"(x[5]), [x6] "+v"(x[6]), [q0] "+v"(qb[0]), [q1] "+v"(qb[1]), [q2] "+v"(qb[2]),
+                     [q3] "+v"(qb[3]), [q4] "+v"(qb[4]), [q5] "+v"(qb[5]), [q6] "+v"(qb[6]), [i] "=&s"(i)
                    : [np] "v"(np), [c] "s"(a.lf_c), [n] "s"(np_max)
                    : "vcc", "scc");
     }
     double w[C];
 #pragma unroll
-    for (int e = 0; e < C; ++e) w[e] = __builtin_fma(a.lf_ch, q[e], -x[e]);
-    double m1l = rows_sumsq<C>(q, 0.0);
-    const double k1 = __builtin_fma(rows_sumsq<C>(w, 0.0), a.lf_idt2, m1l);
+    for (int e = 0; e < C; ++e) w[e] = __builtin_fma(a.lf_ch, qb[e], -x[e]);
+    mb = rows_sumsq<C>(qb, 0.0);
+    const double k1 = __builtin_fma(rows_sumsq<C>(w, 0.0), a.lf_idt2, mb);
     // one reduction for both: lane 7 of the row holds 2 (E1 - E0), lane 15 holds 2 E0 - logc
     const double s2 = row_sum2_l7_l15(k1 - e0l, e0l);
-    E0 = __builtin_fma(s2, 0.5, hlogc);                   // the energy: lane 15
+    Eb = __builtin_fma(s2, 0.5, hlogc);                   // the energy: lane 15
     if (write_row) {
       if (nbuf == 0) row_first = row;
-      park_rows(Ebuf, dEbuf, E0, E0 - Eprev, lane15);
-      if (++nbuf == kRowLanes) {
-        flush_E(kRowLanes);
-        nbuf = 0;
-      }
+      park_rows(Ebuf, dEbuf, Eb, Eb - Ea, lane15);
+      // the count moves outside the flush's per-lane branch (a reset inside it would make the
+      // count a per-lane value for the compiler)
+      const bool full = nbuf + 1 == kRowLanes;
+      if (full) flush_E(kRowLanes);
+      nbuf = full ? 0 : nbuf + 1;
     }
-    Eprev = E0;
     if (it + 1 < a.it1) ring_momentum(it + 1);           // p (x) is dead: the next momentum goes into it
     // the test in lane 7 of each row (where the reduction leaves 2 dE; lnu is the same in the row's
     // lanes); the four bits widened to row masks on the SALU
     const uint64_t b7 = (__builtin_amdgcn_ballot_w64(s2 < 0.0) | __builtin_amdgcn_ballot_w64(lnu < -s2)) & kRowLane7;
     const uint64_t accm = (b7 << 9) - (b7 >> 7);
     const uint64_t rej = ~accm;
-    if (rej != 0) {                                       // uniform; restores the rejecting rows under EXEC
+    if (rej != 0) {                                       // uniform; the rejecting rows take the start state under EXEC
       uint64_t ex;
       asm volatile("s_mov_b64 %[ex], exec\n\t"
                    "s_mov_b64 exec, %[rej]\n\t"
@@ -390,23 +411,22 @@ __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4
                    "v_mov_b64 %[q6], %[i6]\n\t"
                    "v_mov_b64 %[m1], %[m0]\n\t"
                    "s_mov_b64 exec, %[ex]"
-                   : [q0] "+v"(q[0]), [q1] "+v"(q[1]), [q2] "+v"(q[2]), [q3] "+v"(q[3]), [q4] "+v"(q[4]),
-                     [q5] "+v"(q[5]), [q6] "+v"(q[6]), [m1] "+v"(m1l), [ex] "=&s"(ex)
-                   : [rej] "s"(rej), [i0] "v"(qi[0]), [i1] "v"(qi[1]), [i2] "v"(qi[2]), [i3] "v"(qi[3]),
-                     [i4] "v"(qi[4]), [i5] "v"(qi[5]), [i6] "v"(qi[6]), [m0] "v"(m0l));
+                   : [q0] "+v"(qb[0]), [q1] "+v"(qb[1]), [q2] "+v"(qb[2]), [q3] "+v"(qb[3]), [q4] "+v"(qb[4]),
+                     [q5] "+v"(qb[5]), [q6] "+v"(qb[6]), [m1] "+v"(mb), [ex] "=&s"(ex)
+                   : [rej] "s"(rej), [i0] "v"(qa[0]), [i1] "v"(qa[1]), [i2] "v"(qa[2]), [i3] "v"(qa[3]),
+                     [i4] "v"(qa[4]), [i5] "v"(qa[5]), [i6] "v"(qa[6]), [m0] "v"(ma));
     }
-    m0l = m1l;                                            // the potential part of the state kept
     if (write_row && qcb && row >= a.q_row0) {
       char* const rowb = qcb + (int64_t)qslot * a.D * 8;
 #pragma unroll
       for (int j = 0; j < C; ++j)
         if (j < C - 1 ? valid : st6)
-          __builtin_nontemporal_store(q[j], reinterpret_cast<double*>(rowb + qoff) + kRowLanes * j);
+          __builtin_nontemporal_store(qb[j], reinterpret_cast<double*>(rowb + qoff) + kRowLanes * j);
     }
     if (post) add_mask(n_acc, accm); else add_mask(n_acc_wu, accm);
     // a rejection before i_oob = wu - Lc thin <= wu: only the warm-up instance can meet one
     if constexpr (!post) add_mask(n_oob, it < a.i_oob ? rej : 0ull);
-    e0l = rows_sumsq<C>(p, m0l);
+    e0l = rows_sumsq<C>(p, mb);                           // the state kept is in set b
     if (post && ++phase == a.thin) {
       phase = 0;
       ++row;
@@ -414,17 +434,34 @@ __global__ __launch_bounds__(kRowsBlock) __attribute__((amdgpu_waves_per_eu(4, 4
     }
   };
   const int it_mid = min(max(a.wu, a.it0), a.it1);
-  for (int it = a.it0; it < it_mid; ++it) iteration(std::false_type{}, it);
-  for (int it = it_mid; it < a.it1; ++it) iteration(std::true_type{}, it);
+  // Two iterations per trip, one in each role.  A loop that ends after an odd number of iterations
+  // leaves the state in the second set: it is copied back once, so both loops start and the kernel
+  // ends in role 0.
+  auto iterations = [&](auto post_c, int from, int to) __attribute__((always_inline)) {
+    int it = from;
+    for (; it + 1 < to; it += 2) {
+      iteration(post_c, std::false_type{}, it);
+      iteration(post_c, std::true_type{}, it + 1);
+    }
+    if (it < to) {
+      iteration(post_c, std::false_type{}, it);
+#pragma unroll
+      for (int e = 0; e < C; ++e) q[e] = qt[e];
+      ml = mtl;
+      Eprev = Et;
+    }
+  };
+  iterations(std::false_type{}, a.it0, it_mid);
+  iterations(std::true_type{}, it_mid, a.it1);
 
   if (nbuf > 0) flush_E(nbuf);
 #pragma unroll
   for (int j = 0; j < C; ++j)
-    if (j < C - 1 ? valid : st6) qst[kRowLanes * j] = q[j];
+    if (j < C - 1 ? valid : st6) reinterpret_cast<double*>(qstb + qstoff)[kRowLanes * j] = q[j];
   n_lf = row_sum_u32_l15(n_lf);
   n_lf2 = row_sum_u32_l15(n_lf2);
   if (valid && s == kRowLanes - 1) {                      // lane 15: where the row sums leave E and the tallies
-    a.Eprev[c] = Eprev;
+    reinterpret_cast<double*>(reinterpret_cast<char*>(a.Eprev + c0) + 8u * r)[0] = Eprev;
     if (a.cnt) {
       unsigned long long* cs = a.cnt + (c & (HMC_COUNTER_SLOTS - 1)) * HMC_NCOUNTERS;
       if (n_acc) atomicAdd(cs + HMC_CNT_ACCEPT, (unsigned long long)n_acc);
