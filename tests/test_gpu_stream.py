@@ -235,3 +235,42 @@ def test_checkpoint_rejects_other_engine(tmp_path):
         mk(0.2, np.zeros(D)).restore(path)
     with pytest.raises(AssertionError, match="target_sha256"):
         mk(0.1, np.full(D, 0.5)).restore(path)
+
+
+_META_KEYS = {"kind", "N", "D", "n_iter", "warm_up", "thin", "L_chain", "L_low", "L_high", "seed", "rng", "fp_mode",
+              "chain_offset", "d_max", "order_tiles", "dt", "cov_p_sha256", "target_sha256"}
+
+
+@pytest.mark.parametrize("kind,extra", [("RandomEngine", set()), ("NutsEngine", set()), ("MixtureEngine", set()),
+                                        ("LogisticEngine", set()), ("GLMEngine", set()), ("GLMNutsEngine", set()),
+                                        ("GLMEngine", {"adapt_step", "adapt_delta"})])
+def test_checkpoint_meta_format(tmp_path, kind, extra):
+    """The checkpoint format of every engine: _meta() has exactly these keys, `kind` is the class
+    name, and a checkpoint restores into a second identically built engine at the saved it_next."""
+    from hmc_amd import engine as E
+    from hmc_amd.target import GLMTarget, LogisticTarget, MixtureTarget, MVNTarget
+    N, D, n_iter, d_max = 16, 3, 4, 3
+    rs = np.random.RandomState(3)
+    X = rs.standard_normal((8, D))
+    targets = {"RandomEngine": MVNTarget(np.zeros(D), np.diag([1.0, 2.0, 0.5])),
+               "NutsEngine": MVNTarget(np.zeros(D), np.diag([1.0, 2.0, 0.5])),
+               "MixtureEngine": MixtureTarget([0.4, 0.6], np.array([[-1.0] * D, [1.0] * D]), np.ones((2, D))),
+               "LogisticEngine": LogisticTarget(X, [0, 1, 1, 0, 1, 0, 0, 1]),
+               "GLMEngine": GLMTarget(X, [0, 2, 1, 0, 3, 1, 0, 1], family="poisson"),
+               "GLMNutsEngine": GLMTarget(X, [0, 2, 1, 0, 3, 1, 0, 1], family="poisson")}
+    kw = dict(rng="philox", seed=2, adapt_step=True) if extra else dict(rng="philox", seed=2)
+
+    def make():
+        if kind.endswith("NutsEngine"):
+            return getattr(E, kind)(targets[kind], N, n_iter, 1, 1, d_max, 0.1, on_dmax="break", **kw)
+        return getattr(E, kind)(targets[kind], N, n_iter, 1, 1, 5, 20, 0.1, **kw)
+    a, b = make(), make()
+    meta = a._meta()
+    assert set(meta) == _META_KEYS | extra
+    assert meta["kind"] == kind
+    a.init(torch.as_tensor(0.1 * rs.standard_normal((N, D))).cuda())
+    a.run(1, 3)
+    path = str(tmp_path / "meta.npz")
+    a.save(path, 3)
+    assert b.restore(path) == 3
+    assert torch.equal(b.q, a.q)

@@ -13,10 +13,9 @@ import numpy as np
 import torch
 
 from . import _lib as H
-
-
-def _dev(a, device, dtype=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(device)
+from . import descriptors as Dsc
+from .descriptors import dev_tensor as _dev
+from .target import GLMTarget, LogisticTarget, MixtureTarget
 
 
 class RandomEngine:
@@ -60,42 +59,22 @@ class RandomEngine:
     def _descriptors(self, target, cov_p, dt, dense):
         """Target / kinetic descriptors self.T, self.K (their device arrays kept alive on the
         object); returns the target kind."""
-        D, dev = self.D, self.device
-        cov_p = np.diag(np.ones(D)) if cov_p is None else np.asarray(cov_p, dtype=np.float64)
-        self.cov_p = cov_p
-        full_mass = bool(np.any(cov_p - np.diag(np.diag(cov_p))))   # Q3 with a full cov_p
-        diag = target.diagonal and not dense and not full_mass
-        kind = H.HMC_TARGET_DIAG if diag else H.HMC_TARGET_DENSE
-        self._q0 = None if target.zero_mean else _dev(target.q0, dev)
-        if diag:
-            self._prec = None if target.identity else _dev(np.diag(target.prec), dev)
-        else:
-            self._prec = _dev(target.prec, dev)
-        self._minv_full = self._chol_t = self._kick = None
-        if full_mass:
-            # samplers.py:356 (inv_cov_p), :829 (p ~ N(0, cov_p) = C z) and :835-837 (kick by
-            # inv_cov_p . dVdq): host-side constants of the run, like the reference's inv_cov_p
-            minv_full = np.linalg.inv(cov_p)
-            self._minv_full = _dev(minv_full, dev)
-            self._chol_t = _dev(np.linalg.cholesky(cov_p).T, dev)
-            self._kick = _dev(minv_full @ np.asarray(target.prec, dtype=np.float64), dev)
-            self._minv = self._pscale = None
-        else:
-            minv = np.diag(np.linalg.inv(cov_p)).astype(np.float64)      # samplers.py:356
-            ident_mass = bool(np.all(np.diag(cov_p) == 1.0) and np.all(minv == 1.0))
-            self._minv = None if ident_mass else _dev(minv, dev)
-            self._pscale = None if ident_mass else _dev(np.sqrt(np.diag(cov_p)), dev)
-        dt = np.asarray(dt, dtype=np.float64)
-        self.dt = dt
-        if dt.ndim == 0:
-            self._dtv, dts = None, float(dt)
-        else:
-            assert dt.size == D
-            self._dtv, dts = _dev(dt.reshape(-1), dev), 0.0
-        self.T = H.Target(D, kind, H.ptr(self._q0), H.ptr(self._prec), target.logdet_const)
-        self.K = H.Kinetic(H.ptr(self._minv), H.ptr(self._pscale), H.ptr(self._dtv), dts, H.ptr(self._minv_full),
-                           H.ptr(self._chol_t), H.ptr(self._kick))
-        return kind
+        mvn, kin = Dsc.host_descriptors(target, cov_p, dt, dense, chol=True)
+        self.T, self._target_keep = Dsc.upload_mvn(target, mvn, self.device)
+        self._kinetic(cov_p, dt, kin)
+        return mvn.kind
+
+    def _kinetic(self, cov_p, dt, kin):
+        """self.K from the host arrays `kin`, and the values of cov_p and dt a checkpoint records."""
+        self.cov_p, self.dt = Dsc.host_cov_p(cov_p, self.D), np.asarray(dt, dtype=np.float64)
+        self.K, self._kinetic_keep = Dsc.upload_kinetic(kin, self.device)
+        self._full_mass = kin.minv_full is not None
+
+    @staticmethod
+    def _large_d(kind, D):
+        """hmc::big_path (csrc/hmc_big.hip): dense D > 128 (no MFMA tile layout), diagonal D > 2048
+        (more than 16 coordinate pairs per lane of a wave)."""
+        return D > 128 if kind == H.HMC_TARGET_DENSE else (D + 1) // 2 > 16 * 64
 
     def _alloc_workspace(self, kind, order_tiles, random_ws):
         D = self.D
@@ -104,9 +83,8 @@ class RandomEngine:
         # path (dense D > 128, diagonal D > 2048) keeps its chain state there: always allocated (a
         # NUTS run only needs it for hmc_chain_init's start energies, random_ws=False: sized for the
         # init alone, i.e. without the full-cov_p products unless cov_p is full)
-        big = (D > 128) if kind == H.HMC_TARGET_DENSE else ((D + 1) // 2 > 16 * 64)
         L_ = H.lib()
-        if big:
+        if self._large_d(kind, D):
             nbytes = L_.hmc_random_workspace_size_ex(self.T, self.K, self.N)
         elif order_tiles and random_ws:
             nbytes = L_.hmc_random_workspace_size(self.T, self.N)
@@ -148,12 +126,18 @@ class RandomEngine:
     def stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
+    def _init_call(self):
+        """init()'s C entry, its name in error messages, and its arguments between the state and
+        the stream."""
+        return "hmc_chain_init_ws", "hmc_chain_init", (self._order_bytes,)
+
     def init(self, q_start):
         qs = q_start if isinstance(q_start, torch.Tensor) else _dev(np.asarray(q_start).reshape(self.N, self.D),
                                                                     self.device)
         self._qs = qs.to(self.device, torch.float64).contiguous()
-        H.check(H.lib().hmc_chain_init_ws(self.T, self.K, self.schedule(1, 1), self._replay, H.ptr(self._qs), self.S,
-                                          self._order_bytes, self.stream()), "hmc_chain_init")
+        entry, what, tail = self._init_call()
+        H.check(getattr(H.lib(), entry)(self.T, self.K, self.schedule(1, 1), self._replay, H.ptr(self._qs), self.S,
+                                        *tail, self.stream()), what)
 
     def run(self, it0, it1):
         """Iterations [it0, it1) of every chain in ONE fused kernel launch."""
@@ -237,16 +221,13 @@ class RandomEngine:
     def _meta(self):
         """Everything that decides the chain's next values: a checkpoint restores only into an
         engine with the same schedule, step size, mass matrix and target."""
-        h = hashlib.sha256()
-        for a in self._target_arrays():
-            h.update(np.ascontiguousarray(a, dtype=np.float64).tobytes())
         return dict(kind=type(self).__name__, N=self.N, D=self.D, n_iter=self.n_iter, warm_up=self.warm_up,
                     thin=self.thin, L_chain=self.L_chain, L_low=self.L_low, L_high=self.L_high, seed=self.seed,
                     rng=self.rng, fp_mode=self.fp_mode, chain_offset=self.chain_offset, d_max=self.d_max,
                     order_tiles=self._order is not None,
                     dt=np.asarray(self.dt, dtype=np.float64).ravel().tolist(),
                     cov_p_sha256=hashlib.sha256(np.ascontiguousarray(self.cov_p, np.float64).tobytes()).hexdigest(),
-                    target_sha256=h.hexdigest())
+                    target_sha256=Dsc.fingerprint(self._target_arrays()))
 
     def save(self, path, it_next, include_chain=True, diag=None):
         """Checkpoint after iteration it_next - 1 (.npz, no pickles).  Philox draws are keyed by
@@ -321,13 +302,11 @@ class RandomEngine:
 
 class _KernelTargetEngine(RandomEngine):
     """What the engines of the targets with kernels of their own share (MixtureEngine,
-    LogisticEngine): RandomEngine's surface, state and outputs, a target descriptor of their own in
-    place of the MVN one, a diagonal cov_p only, no workspace, and a pair of C entries that take that
-    descriptor.  `fp_mode` is accepted and changes nothing (one arithmetic: exp / log cannot be
-    bit-identical to NumPy's)."""
-
-    _init_entry = _run_entry = None      # names of the hmc_*_chain_init / hmc_*_random_iters entries
-    _what = "these"
+    LogisticEngine, GLMEngine): RandomEngine's surface, state and outputs, a target descriptor of
+    their own in place of the MVN one, a diagonal cov_p only, no workspace, and a pair of C entries
+    that take that descriptor: all of it read from the target's row of KERNEL_TARGETS (`self.row`).
+    `fp_mode` is accepted and changes nothing (one arithmetic: exp / log cannot be bit-identical to
+    NumPy's)."""
 
     def __init__(self, target, n_chains, n_iter, warm_up, thin, L_low, L_high, dt, cov_p=None, rng="philox",
                  seed=0, fp_mode="fast", chain_offset=0, store_chain=True, store_energy=True, n_save=0,
@@ -337,45 +316,34 @@ class _KernelTargetEngine(RandomEngine):
                          store_energy=store_energy, n_save=n_save, device=device)
 
     @classmethod
-    def _check_diag_mass(cls, cov_p):
-        if cov_p is not None:
-            cov_p = np.asarray(cov_p, dtype=np.float64)
-            if np.any(cov_p - np.diag(np.diag(cov_p))):
-                raise NotImplementedError("%s kernels: a full cov_p is not supported (diagonal only)" % cls._what)
+    def check_supported(cls, target, cov_p):
+        """NotImplementedError, before anything touches the device, for what the kernels do not take."""
+        row = kernel_target(target)
+        row.check(target)
+        if cov_p is not None and Dsc.full_mass(np.asarray(cov_p, dtype=np.float64)):
+            raise NotImplementedError("%s kernels: a full cov_p is not supported (diagonal only)" % row.name)
 
-    def _kinetic(self, cov_p, dt):
-        """self.K for a diagonal cov_p (its device arrays kept alive on the object)."""
-        D, dev = self.D, self.device
-        cov_p = np.diag(np.ones(D)) if cov_p is None else np.asarray(cov_p, dtype=np.float64)
-        self.cov_p = cov_p
-        minv = np.diag(np.linalg.inv(cov_p)).astype(np.float64)          # samplers.py:356
-        ident_mass = bool(np.all(np.diag(cov_p) == 1.0) and np.all(minv == 1.0))
-        self._minv = None if ident_mass else _dev(minv, dev)
-        self._pscale = None if ident_mass else _dev(np.sqrt(np.diag(cov_p)), dev)
-        self._minv_full = None
-        dt = np.asarray(dt, dtype=np.float64)
-        self.dt = dt
-        if dt.ndim == 0:
-            self._dtv, dts = None, float(dt)
-        else:
-            assert dt.size == D
-            self._dtv, dts = _dev(dt.reshape(-1), dev), 0.0
-        self.K = H.Kinetic(H.ptr(self._minv), H.ptr(self._pscale), H.ptr(self._dtv), dts, None, None, None)
+    def _descriptors(self, target, cov_p, dt, dense):
+        self.check_supported(target, cov_p)
+        self.row = kernel_target(target)
+        assert isinstance(self, self.row.engine), "%s does not run %s targets" % (type(self).__name__, self.row.name)
+        self.T, self._target_keep = self.row.upload(target, self.device)
+        self._kinetic(cov_p, dt, Dsc.host_kinetic(self.D, cov_p, dt))
+        return None
+
+    def _target_arrays(self):
+        return self.row.fingerprint_arrays(self.t)
 
     def _alloc_workspace(self, kind, order_tiles, random_ws):
         self._order, self._order_bytes = None, 0        # hmc_state.order is ignored by these calls
 
-    def init(self, q_start):
-        qs = q_start if isinstance(q_start, torch.Tensor) else _dev(np.asarray(q_start).reshape(self.N, self.D),
-                                                                    self.device)
-        self._qs = qs.to(self.device, torch.float64).contiguous()
-        H.check(getattr(H.lib(), self._init_entry)(self.T, self.K, self.schedule(1, 1), self._replay, H.ptr(self._qs),
-                                                   self.S, self.stream()), self._init_entry)
+    def _init_call(self):
+        return self.row.init, self.row.init, ()
 
     def run(self, it0, it1):
         """Iterations [it0, it1) of every chain in ONE fused kernel launch."""
-        H.check(getattr(H.lib(), self._run_entry)(self.T, self.K, self.schedule(it0, it1), self._replay, self.S,
-                                                  self.stream()), self._run_entry)
+        H.check(getattr(H.lib(), self.row.iters)(self.T, self.K, self.schedule(it0, it1), self._replay, self.S,
+                                                 self.stream()), self.row.iters)
 
 
 class MixtureEngine(_KernelTargetEngine):
@@ -384,27 +352,6 @@ class MixtureEngine(_KernelTargetEngine):
     mixture descriptor in place of the MVN one.  Diagonal cov_p only, D <= 512, K <= 8; `fp_mode`
     is accepted and changes nothing (one arithmetic: exp / log cannot be bit-identical to NumPy's)."""
 
-    _init_entry, _run_entry, _what = "hmc_mix_chain_init", "hmc_mix_random_iters", "mixture"
-
-    @classmethod
-    def check_supported(cls, target, cov_p):
-        """NotImplementedError, before anything touches the device, for what the kernels do not take."""
-        if target.D > H.MIX_MAX_D or target.K > H.MIX_MAX_COMPONENTS:
-            raise NotImplementedError("mixture kernels: D=%d, K=%d (D <= %d, K <= %d)"
-                                      % (target.D, target.K, H.MIX_MAX_D, H.MIX_MAX_COMPONENTS))
-        cls._check_diag_mass(cov_p)
-
-    def _descriptors(self, target, cov_p, dt, dense):
-        self.check_supported(target, cov_p)
-        self._mix = [_dev(a, self.device) for a in (target.logw, target.mu, target.prec, target.logdet_const)]
-        self._kinetic(cov_p, dt)
-        self.T = H.Mixture(self.D, target.K, *[H.ptr(x) for x in self._mix])
-        return None
-
-    def _target_arrays(self):
-        t = self.t
-        return (t.logw, t.mu, t.prec, t.logdet_const)
-
 
 class LogisticEngine(_KernelTargetEngine):
     """Chain batch of the Random-trajectory sampler on a LogisticTarget (hmc_logit_chain_init /
@@ -412,36 +359,12 @@ class LogisticEngine(_KernelTargetEngine):
     on the f64 matrix cores).  Diagonal cov_p only, D <= 128, n <= 2^20; `fp_mode` is accepted and
     changes nothing.  A checkpoint fingerprints the data (X, y, 1 / prior_var)."""
 
-    _init_entry, _run_entry, _what = "hmc_logit_chain_init", "hmc_logit_random_iters", "logistic"
-
-    @classmethod
-    def check_supported(cls, target, cov_p):
-        """NotImplementedError, before anything touches the device, for what the kernels do not take."""
-        if target.D > H.LOGIT_MAX_D or target.n > H.LOGIT_MAX_N:
-            raise NotImplementedError("logistic kernels: D=%d, n=%d (D <= %d, n <= %d)"
-                                      % (target.D, target.n, H.LOGIT_MAX_D, H.LOGIT_MAX_N))
-        cls._check_diag_mass(cov_p)
-
-    def _descriptors(self, target, cov_p, dt, dense):
-        self.check_supported(target, cov_p)
-        # X as it is, row-major with ldx = D: the kernel clamps its reads to [n][D]
-        self._data = [_dev(a, self.device) for a in (target.X, target.y, target.prior_prec)]
-        self._kinetic(cov_p, dt)
-        self.T = H.Logistic(self.D, target.n, self.D, *[H.ptr(x) for x in self._data])
-        return None
-
-    def _target_arrays(self):
-        t = self.t
-        return (t.X, t.y, t.prior_prec)
-
 
 class GLMEngine(_KernelTargetEngine):
     """Chain batch of the Random-trajectory sampler on a GLMTarget (hmc_glm_chain_init /
     hmc_glm_random_iters: the logistic kernels of csrc/hmc_logit.hip with the family as a template
     parameter).  LogisticEngine's limits: diagonal cov_p only, D <= 128, n <= 2^20; `fp_mode` is
     accepted and changes nothing.  A checkpoint fingerprints the data and the family."""
-
-    _init_entry, _run_entry, _what = "hmc_glm_chain_init", "hmc_glm_random_iters", "GLM"
 
     def __init__(self, *args, adapt_step=False, adapt_delta=0.8, step_scale0=None, **kw):
         """adapt_step: every chain adapts a multiplier of `dt` during warm-up (iterations
@@ -500,47 +423,18 @@ class GLMEngine(_KernelTargetEngine):
         H.check(H.lib().hmc_glm_random_iters_adapt(self.T, self.K, self.schedule(it0, it1), self._replay, self.S,
                                                    self._adapt, self.stream()), "hmc_glm_random_iters_adapt")
 
-    @classmethod
-    def check_supported(cls, target, cov_p):
-        """NotImplementedError, before anything touches the device, for what the kernels do not take."""
-        if target.D > H.LOGIT_MAX_D or target.n > H.LOGIT_MAX_N:
-            raise NotImplementedError("GLM kernels: D=%d, n=%d (D <= %d, n <= %d)"
-                                      % (target.D, target.n, H.LOGIT_MAX_D, H.LOGIT_MAX_N))
-        cls._check_diag_mass(cov_p)
 
-    def _descriptors(self, target, cov_p, dt, dense):
-        self.check_supported(target, cov_p)
-        # X as it is, row-major with ldx = D: the kernel clamps its reads to [n][D]
-        self._data = [_dev(a, self.device) for a in (target.X, target.y, target.prior_prec)]
-        self._kinetic(cov_p, dt)
-        self.T = H.GLM(self.D, target.n, self.D, *[H.ptr(x) for x in self._data], target.family_id)
-        return None
+class _NutsSurface:
+    """What the NUTS engines share on top of their Random base: the tree's depth limit and what
+    happens at it (`d_max`, `on_dmax`), the replay tape in place of (L, log u), and the tree
+    workspace `ws`, allocated zeroed from the engine's size query, which stays on the device."""
 
-    def _target_arrays(self):
-        t = self.t
-        return (t.X, t.y, t.prior_prec, np.float64(t.family_id))
-
-
-class GLMNutsEngine(GLMEngine):
-    """Chain batch of the No-U-Turn sampler on a GLMTarget (hmc_glm_nuts_iters, csrc/hmc_glm_nuts.hip:
-    one wave steps a tile of 16 chains, each its own tree).  NutsEngine's surface: `d_max`, `on_dmax`,
-    `set_replay(p0, P, tape)`, `run(it0, it1)`; the workspace (tree vectors of every chain, then the
-    replay-tape cursors) is allocated zeroed from the size query and stays on the device.  `init()`
-    is GLMEngine's (hmc_glm_chain_init serves both samplers)."""
-
-    def __init__(self, target, n_chains, n_iter, warm_up, thin, d_max, dt, cov_p=None, rng="philox", seed=0,
-                 fp_mode="fast", chain_offset=0, store_chain=True, store_energy=True, on_dmax="raise",
-                 device=None, iters_per_call=None, adapt_step=False, adapt_delta=0.8, step_scale0=None):
-        super().__init__(target, n_chains, n_iter, warm_up, thin, 5, 20, dt, cov_p=cov_p, rng=rng, seed=seed,
-                         fp_mode=fp_mode, chain_offset=chain_offset, store_chain=store_chain,
-                         store_energy=store_energy, n_save=0, device=device, adapt_step=adapt_step,
-                         adapt_delta=adapt_delta, step_scale0=step_scale0)
+    def _nuts_setup(self, d_max, on_dmax):
         assert on_dmax in ("raise", "break")
         self.d_max = int(d_max)
         self.on_dmax = 0 if on_dmax == "raise" else 1
-        nbytes = H.lib().hmc_glm_nuts_workspace_size(self.D, self.N, self.d_max)
-        if nbytes <= 0 and self.N > 0:
-            raise NotImplementedError("GLM NUTS kernel: d_max=%d not supported (1 <= d_max <= 30)" % self.d_max)
+
+    def _alloc_ws(self, nbytes):
         self.ws = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=self.device)
 
     def set_replay(self, p0, P, tape):
@@ -550,6 +444,26 @@ class GLMNutsEngine(GLMEngine):
         self._streams = [_dev(p0, dev), _dev(P, dev), _dev(tape, dev)]
         self._replay = H.Replay(H.ptr(self._streams[0]), H.ptr(self._streams[1]), None, None,
                                 H.ptr(self._streams[2]), tape.shape[1])
+
+
+class GLMNutsEngine(_NutsSurface, GLMEngine):
+    """Chain batch of the No-U-Turn sampler on a GLMTarget (hmc_glm_nuts_iters, csrc/hmc_glm_nuts.hip:
+    one wave steps a tile of 16 chains, each its own tree).  NutsEngine's surface: `d_max`, `on_dmax`,
+    `set_replay(p0, P, tape)`, `run(it0, it1)`; the workspace holds the tree vectors of every chain,
+    then the replay-tape cursors.  `init()` is GLMEngine's (hmc_glm_chain_init serves both samplers)."""
+
+    def __init__(self, target, n_chains, n_iter, warm_up, thin, d_max, dt, cov_p=None, rng="philox", seed=0,
+                 fp_mode="fast", chain_offset=0, store_chain=True, store_energy=True, on_dmax="raise",
+                 device=None, iters_per_call=None, adapt_step=False, adapt_delta=0.8, step_scale0=None):
+        super().__init__(target, n_chains, n_iter, warm_up, thin, 5, 20, dt, cov_p=cov_p, rng=rng, seed=seed,
+                         fp_mode=fp_mode, chain_offset=chain_offset, store_chain=store_chain,
+                         store_energy=store_energy, n_save=0, device=device, adapt_step=adapt_step,
+                         adapt_delta=adapt_delta, step_scale0=step_scale0)
+        self._nuts_setup(d_max, on_dmax)
+        nbytes = H.lib().hmc_glm_nuts_workspace_size(self.D, self.N, self.d_max)
+        if nbytes <= 0 and self.N > 0:
+            raise NotImplementedError("GLM NUTS kernel: d_max=%d not supported (1 <= d_max <= 30)" % self.d_max)
+        self._alloc_ws(nbytes)
 
     def run(self, it0, it1):
         """Iterations [it0, it1) of every chain in one launch."""
@@ -562,7 +476,7 @@ class GLMNutsEngine(GLMEngine):
                                            H.ptr(self.ws), self.ws.numel() * 8, self.stream()), "hmc_glm_nuts_iters")
 
 
-class NutsEngine(RandomEngine):
+class NutsEngine(_NutsSurface, RandomEngine):
     """Chain batch of the No-U-Turn sampler (samplers.py:495-808) on the dense-precision
     MFMA kernel (hmc_nuts_iters).  Diagonal targets are passed as dense precisions.
     `run(it0, it1)` advances every chain through iterations [it0, it1) in one launch; the
@@ -576,26 +490,16 @@ class NutsEngine(RandomEngine):
                          fp_mode=fp_mode, chain_offset=chain_offset, store_chain=store_chain,
                          store_energy=store_energy, n_save=0, device=device, dense=True, order_tiles=False,
                          random_ws=False)
-        assert on_dmax in ("raise", "break")
-        self.d_max = int(d_max)
-        self.on_dmax = 0 if on_dmax == "raise" else 1
+        self._nuts_setup(d_max, on_dmax)
         # the Philox momenta drawn ahead are sized for the longest run() call (at most 32 iterations
         # are drawn per launch); replay tapes and a full cov_p draw in the kernel and need none
         self.iters_per_call = int(iters_per_call or n_iter)
-        philox_mom = int(rng == "philox" and self._minv_full is None)
+        philox_mom = int(rng == "philox" and not self._full_mass)
         nbytes = H.lib().hmc_nuts_workspace_size_ex(self.D, self.N, self.d_max, max(1, self.iters_per_call),
                                                     philox_mom)
         if nbytes <= 0:
             raise NotImplementedError("NUTS kernel: d_max=%d not supported (1 <= d_max <= 30)" % self.d_max)
-        self.ws = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=self.device)
-
-    def set_replay(self, p0, P, tape):
-        """Host-replayed draws: p0 (N,D), p (N,Niter,D), tape (N,T) directions/uniforms in order."""
-        dev = self.device
-        tape = np.ascontiguousarray(tape, dtype=np.float64)
-        self._streams = [_dev(p0, dev), _dev(P, dev), _dev(tape, dev)]
-        self._replay = H.Replay(H.ptr(self._streams[0]), H.ptr(self._streams[1]), None, None,
-                                H.ptr(self._streams[2]), tape.shape[1])
+        self._alloc_ws(nbytes)
 
     def run(self, it0, it1):
         if it1 - it0 > self.iters_per_call:
@@ -604,3 +508,28 @@ class NutsEngine(RandomEngine):
         # the sized entry checks the workspace against what this call needs (include/hmc.h)
         H.check(H.lib().hmc_nuts_iters_ws(self.T, self.K, self.schedule(it0, it1), self._replay, self.S,
                                           H.ptr(self.ws), self.ws.numel() * 8, self.stream()), "hmc_nuts_iters_ws")
+
+
+# Targets that are not MVN and have kernels of their own (descriptors.KernelTarget): the one place
+# that lists a target's arrays, for the device descriptor and for the checkpoint fingerprint alike.
+_GLM_LIMITS = (("D", H.LOGIT_MAX_D), ("n", H.LOGIT_MAX_N))
+_GLM_HEAD = lambda t: (t.D, t.n, t.D)       # noqa: E731  (D, n, ldx)
+KERNEL_TARGETS = {
+    MixtureTarget: Dsc.KernelTarget(
+        "mixture", ("logw", "mu", "prec", "logdet_const"), (), H.Mixture, lambda t: (t.D, t.K),
+        (("D", H.MIX_MAX_D), ("K", H.MIX_MAX_COMPONENTS)),
+        "hmc_mix_chain_init", "hmc_mix_random_iters", "hmc_mix_leapfrog", "hmc_mix_energy", MixtureEngine, None),
+    LogisticTarget: Dsc.KernelTarget(
+        "logistic", ("X", "y", "prior_prec"), (), H.Logistic, _GLM_HEAD, _GLM_LIMITS,
+        "hmc_logit_chain_init", "hmc_logit_random_iters", "hmc_logit_leapfrog", "hmc_logit_energy",
+        LogisticEngine, None),
+    GLMTarget: Dsc.KernelTarget(
+        "GLM", ("X", "y", "prior_prec"), ("family_id",), H.GLM, _GLM_HEAD, _GLM_LIMITS,
+        "hmc_glm_chain_init", "hmc_glm_random_iters", "hmc_glm_leapfrog", "hmc_glm_energy", GLMEngine,
+        GLMNutsEngine),
+}
+
+
+def kernel_target(target):
+    """The KERNEL_TARGETS row of `target`; None for an MVN target."""
+    return next((row for cls, row in KERNEL_TARGETS.items() if isinstance(target, cls)), None)

@@ -18,6 +18,7 @@ from math import lgamma
 import numpy as np
 
 from . import _lib as H
+from .views import SamplesView
 
 FAMILIES = {"bernoulli": H.HMC_GLM_BERNOULLI, "poisson": H.HMC_GLM_POISSON}
 
@@ -41,31 +42,10 @@ def glm_predictive_partials(X, y, family, samples, rows=slice(1, None), device=N
     a device tensor, else the current device)."""
     import torch
     fam = _family_id(family)
-    if not isinstance(samples, torch.Tensor):
-        samples = torch.as_tensor(np.asarray(samples, dtype=np.float64))
-    if samples.dim() != 3:
-        raise AssertionError("samples must be [N][L][D]")
-    if samples.dtype != torch.float64:
-        raise AssertionError("samples must be float64")
-    if device is None:
-        if samples.is_cuda:
-            device = samples.device
-        elif isinstance(X, torch.Tensor) and X.is_cuda:
-            device = X.device
-        else:
-            device = torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    if not samples.is_cuda:
-        samples = samples.to(device)
-    N, L, D = samples.shape
-    if D > 1 and samples.stride(2) != 1:
-        raise AssertionError("samples: the last dimension must be contiguous")
-    if not isinstance(rows, slice):
-        raise AssertionError("rows must be a slice")
-    begin, end, step = rows.indices(L)
-    if step < 1:
-        raise AssertionError("rows must have a positive step")
-    end = max(end, begin)
+    if device is None and not getattr(samples, "is_cuda", False) and isinstance(X, torch.Tensor) and X.is_cuda:
+        device = X.device                          # host samples go where X is
+    view = SamplesView(samples, rows, device)
+    device, D, S = view.device, view.D, view.M
 
     def up(a):
         if isinstance(a, torch.Tensor):
@@ -80,8 +60,6 @@ def glm_predictive_partials(X, y, family, samples, rows=slice(1, None), device=N
         yd = up(y)
         if yd.shape != (n_eval,):
             raise AssertionError("y must be (n_eval,)")
-    n_rows = len(range(begin, end, step))
-    S = N * n_rows
     L_ = H.lib()
     out = torch.zeros((n_eval, H.PRED_STRIDE), dtype=torch.float64, device=device)
     if n_eval == 0 or S == 0:
@@ -92,12 +70,9 @@ def glm_predictive_partials(X, y, family, samples, rows=slice(1, None), device=N
                                   % (D, H.LOGIT_MAX_D, n_eval, H.LOGIT_MAX_N))
     ws = torch.empty(nbytes // 8, dtype=torch.float64, device=device)
     G = H.GLM(D, n_eval, Xd.stride(0) if n_eval > 1 else D, H.ptr(Xd), H.ptr(yd), None, fam)
-    cs = samples.stride(0) if N > 1 else 0
-    rs = samples.stride(1) if L > 1 else D
-    Sm = H.Samples(H.ptr(samples), N, cs, rs, begin, end, step)
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream(device).cuda_stream
-        H.check(L_.hmc_glm_predictive(ctypes.byref(G), ctypes.byref(Sm), H.ptr(out), H.ptr(ws), nbytes, stream),
+        H.check(L_.hmc_glm_predictive(ctypes.byref(G), ctypes.byref(view.c), H.ptr(out), H.ptr(ws), nbytes, stream),
                 "hmc_glm_predictive")
         return out.cpu().numpy()
 

@@ -16,41 +16,7 @@ import ctypes
 import numpy as np
 
 from . import _lib as H
-
-
-class _View:
-    """samples[:, rows, :] as an hmc_samples view on the device."""
-
-    def __init__(self, samples, rows, device):
-        import torch
-        if not isinstance(samples, torch.Tensor):
-            samples = torch.as_tensor(np.asarray(samples, dtype=np.float64))
-        if samples.dim() != 3:
-            raise AssertionError("samples must be [N][L][D]")
-        if samples.dtype != torch.float64:
-            raise AssertionError("samples must be float64")
-        if device is None:
-            device = samples.device if samples.is_cuda else torch.device("cuda", torch.cuda.current_device())
-        self.device = torch.device(device)
-        if not samples.is_cuda:
-            samples = samples.to(self.device)
-        N, L, D = samples.shape
-        if D < 1:
-            raise AssertionError("samples must have D >= 1")
-        if D > 1 and samples.stride(2) != 1:
-            raise AssertionError("samples: the last dimension must be contiguous")
-        if not isinstance(rows, slice):
-            raise AssertionError("rows must be a slice")
-        begin, end, step = rows.indices(L)
-        if step < 1:
-            raise AssertionError("rows must have a positive step")
-        end = max(end, begin)
-        self.samples = samples                      # keeps the storage alive
-        self.D = D
-        self.M = N * len(range(begin, end, step))
-        cs = samples.stride(0) if N > 1 else 0
-        rs = samples.stride(1) if L > 1 else D
-        self.c = H.Samples(H.ptr(samples), N, cs, rs, begin, end, step)
+from .views import SamplesView as _View
 
 
 def _allreduce(x, group):
@@ -118,7 +84,7 @@ def order_stats(samples, ranks, rows=slice(1, None), group=None, device=None):
     `group`); more than 8 run as several calls.  group: a torch.distributed process group whose ranks
     each pass their own chains; None reads this process's samples alone.  device: where a host
     `samples` goes (default: the current device)."""
-    view = _View(samples, rows, device)
+    view = _View(samples, rows, device, min_D=1)
     M = _total(view, group)
     ranks = _check_ranks(ranks, M)
     if not ranks:
@@ -152,7 +118,7 @@ def quantiles(samples, probs, rows=slice(1, None), group=None, device=None):
     a (len(probs), D) NumPy array, from exact order statistics selected on the device and NumPy's
     lerp of x_(lo) and x_(hi) on the host.  A dimension that holds a NaN gives NaN for every
     probability (its largest order statistic is then NaN).  Arguments as `order_stats`."""
-    view = _View(samples, rows, device)
+    view = _View(samples, rows, device, min_D=1)
     M = _total(view, group)
     if M < 1:
         raise AssertionError("quantiles of an empty sample set")

@@ -24,40 +24,12 @@ import numpy as np
 import torch
 
 from . import _lib as H
+from . import descriptors as Dsc
+from .descriptors import dev_tensor as _dev_tensor
 from .diagnostics import StreamingDiagnostics
-from .engine import GLMEngine, GLMNutsEngine, LogisticEngine, MixtureEngine, NutsEngine, RandomEngine
+from .engine import NutsEngine, RandomEngine, kernel_target
 from .target import GLMTarget, LogisticTarget, MixtureTarget, MVNTarget, probe_closures  # noqa: F401
 from . import utils as U
-
-
-def _dev_tensor(a, device, dtype=torch.float64):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(device)
-
-
-def _mixture_descriptor(t, up):
-    keep = [up(a) for a in (t.logw, t.mu, t.prec, t.logdet_const)]
-    return H.Mixture(t.D, t.K, *[H.ptr(x) for x in keep]), keep
-
-
-def _logistic_descriptor(t, up):
-    keep = [up(a) for a in (t.X, t.y, t.prior_prec)]
-    return H.Logistic(t.D, t.n, t.D, *[H.ptr(x) for x in keep]), keep
-
-
-def _glm_descriptor(t, up):
-    keep = [up(a) for a in (t.X, t.y, t.prior_prec)]
-    return H.GLM(t.D, t.n, t.D, *[H.ptr(x) for x in keep], t.family_id), keep
-
-
-# Targets that are not MVN and have kernels of their own: (name, engine, device descriptor for the
-# row-wise calls, leapfrog entry, energy entry, NUTS engine or None).  A diagonal cov_p only; the
-# Random sampler, and NUTS where the target has a NUTS engine.
-_KERNEL_TARGETS = {
-    MixtureTarget: ("mixture", MixtureEngine, _mixture_descriptor, "hmc_mix_leapfrog", "hmc_mix_energy", None),
-    LogisticTarget: ("logistic", LogisticEngine, _logistic_descriptor, "hmc_logit_leapfrog", "hmc_logit_energy",
-                     None),
-    GLMTarget: ("GLM", GLMEngine, _glm_descriptor, "hmc_glm_leapfrog", "hmc_glm_energy", GLMNutsEngine),
-}
 
 
 class sampler(object):
@@ -197,13 +169,12 @@ class HMC_sampler(sampler):
                 self.V = target.V
             if self.dVdq is None:
                 self.dVdq = target.dVdq
-        self._kernel_target = next((v for k, v in _KERNEL_TARGETS.items() if isinstance(target, k)), None)  # None: MVN
-        if self._kernel_target:
-            name, engine = self._kernel_target[:2]
+        self._kernel_target = row = kernel_target(target)       # engine.KERNEL_TARGETS; None: MVN
+        if row:
             assert target.D == self.D
-            if self.sampler_type == "NUTS" and self._kernel_target[5] is None:
-                raise NotImplementedError("NUTS on a %s target is not supported (sampler_type='Random')" % name)
-            engine.check_supported(target, self.cov_p)
+            if self.sampler_type == "NUTS" and row.nuts_engine is None:
+                raise NotImplementedError("NUTS on a %s target is not supported (sampler_type='Random')" % row.name)
+            row.engine.check_supported(target, self.cov_p)
         # step-size adaptation: the GLM kernels alone have the ADAPT forms
         self._adapt_kw = {}
         if adapt_step or step_scale0 is not None:
@@ -224,57 +195,27 @@ class HMC_sampler(sampler):
             self._target = probe_closures(self.D, self.V, self.dVdq)
         return self._target
 
-    def _kernel_target_descriptors(self):
-        """The target's own descriptor (hmc_mixture / hmc_logistic) + hmc_kinetic (diagonal cov_p)
-        for the row-wise calls."""
-        t, dev = self._target, self.device
-        cov_p = np.asarray(self.cov_p, dtype=np.float64)
-        M, keep = self._kernel_target[2](t, lambda a: _dev_tensor(a, dev))
-        minv_d = np.diag(self.inv_cov_p).astype(np.float64)
-        ident_mass = np.all(np.diag(cov_p) == 1.0) and np.all(minv_d == 1.0)
-        minv = None if ident_mass else _dev_tensor(minv_d, dev)
-        dt = np.asarray(self.dt, dtype=np.float64)
-        if dt.ndim == 0:
-            dtv, dts = None, float(dt)
+    def _row_call(self, which, rows, out_shapes, what=None, extra=()):
+        """The row-wise C call `which` ("leapfrog" | "energy") of this target's kernels on the host
+        arrays `rows`; returns its outputs, of shapes `out_shapes`, as NumPy arrays.  `what` names
+        the call in error messages (default: the entry); `extra`: arguments before the stream.
+        p_chol_t is not built: these calls draw no momenta, so a cov_p with an inverse and no
+        Cholesky factor works here."""
+        dev, row = self.device, self._kernel_target
+        if row:
+            T, keep = row.upload(self._target, dev)
+            kin = Dsc.host_kinetic(self.D, self.cov_p, self.dt)
+            entry = getattr(row, which)
         else:
-            assert dt.size == self.D
-            dtv, dts = _dev_tensor(dt.reshape(-1), dev), 0.0
-        keep += [minv, dtv]
-        return M, H.Kinetic(H.ptr(minv), None, H.ptr(dtv), dts, None, None, None), keep
-
-    def _descriptors(self):
-        t = self.target()
-        dev = self.device
-        keep = []
-        cov_p = np.asarray(self.cov_p, dtype=np.float64)
-        full_mass = bool(np.any(cov_p - np.diag(np.diag(cov_p))))
-        diag = t.diagonal and not full_mass
-        kind = H.HMC_TARGET_DIAG if diag else H.HMC_TARGET_DENSE
-        q0 = None if t.zero_mean else _dev_tensor(t.q0, dev)
-        if diag:
-            prec = None if t.identity else _dev_tensor(np.diag(t.prec), dev)
-        else:
-            prec = _dev_tensor(t.prec, dev)
-        minv_full = None
-        if full_mass:                     # samplers.py:356, :835-837 with a full inv_cov_p
-            minv = pscale = None
-            minv_full = _dev_tensor(self.inv_cov_p, dev)
-        else:
-            minv_d = np.diag(self.inv_cov_p).astype(np.float64)
-            ident_mass = np.all(np.diag(cov_p) == 1.0) and np.all(minv_d == 1.0)
-            minv = None if ident_mass else _dev_tensor(minv_d, dev)
-            pscale = None if ident_mass else _dev_tensor(np.sqrt(np.diag(cov_p)), dev)
-        dt = np.asarray(self.dt, dtype=np.float64)
-        if dt.ndim == 0:
-            dtv, dts = None, float(dt)
-        else:
-            assert dt.size == self.D
-            dtv, dts = _dev_tensor(dt.reshape(-1), dev), 0.0
-        kick = None if minv_full is None else _dev_tensor(self.inv_cov_p @ np.asarray(t.prec, np.float64), dev)
-        keep += [q0, prec, minv, pscale, dtv, minv_full, kick]
-        T = H.Target(self.D, kind, H.ptr(q0), H.ptr(prec), t.logdet_const)
-        K = H.Kinetic(H.ptr(minv), H.ptr(pscale), H.ptr(dtv), dts, H.ptr(minv_full), None, H.ptr(kick))
-        return T, K, keep
+            mvn, kin = Dsc.host_descriptors(self.target(), self.cov_p, self.dt)
+            T, keep = Dsc.upload_mvn(self.target(), mvn, dev)
+            entry = "hmc_" + which
+        K, keep_k = Dsc.upload_kinetic(kin, dev)
+        ins = [_dev_tensor(r, dev) for r in rows]
+        outs = [torch.empty(shape, dtype=torch.float64, device=dev) for shape in out_shapes]
+        H.check(getattr(H.lib(), entry)(T, K, rows[0].shape[0], *[H.ptr(x) for x in ins + outs], *extra,
+                                        torch.cuda.current_stream(dev).cuda_stream), what or entry)
+        return [o.cpu().numpy() for o in outs]
 
     # ------------------------------------------------------------------ public API
     def gen_sample(self, q_start, N_save_chain0=0, verbose=True):
@@ -323,7 +264,7 @@ class HMC_sampler(sampler):
         torch.cuda.set_device(self.device)
         n_save = int(N_save_chain0) if N_save_chain0 > 0 else 0
         # the target's own kernels (hmc_mix.hip, hmc_logit.hip) or the MVN kernels
-        engine = self._kernel_target[1] if self._kernel_target else RandomEngine
+        engine = self._kernel_target.engine if self._kernel_target else RandomEngine
         eng = engine(self.target(), self.Nchain, self.Niter, self.warm_up_num, self.thin_rate, self.L_low,
                      self.L_high, self.dt, cov_p=self.cov_p, rng=self.rng, seed=self.seed,
                      fp_mode=self.fp_mode, chain_offset=self.chain_offset, store_chain=self.store_chain,
@@ -389,17 +330,13 @@ class HMC_sampler(sampler):
     # ------------------------------------------------------------------ posterior predictive / WAIC
     def _predictive_partials(self, X, y, what):
         """Records of hmc_amd.predictive over rows 1.. of every chain (the start row is dropped, as
-        compute_convergence_stats does): from q_chain_device where the run left it, else q_chain."""
+        compute_convergence_stats does): of _stored_samples."""
         from . import predictive as P
         t = self._target
         if not isinstance(t, GLMTarget):
             raise NotImplementedError("%s is supported for a GLMTarget only" % what)
-        src = getattr(self, "q_chain_device", None)
-        if src is None and getattr(self, "engine", None) is not None:
-            src = self.q_chain
-        if src is None:
-            raise RuntimeError("%s needs the samples of a run: call gen_sample first (with store_chain)" % what)
-        return P.glm_predictive_partials(X, y, t.family, src, rows=slice(1, None), device=self.device)
+        return P.glm_predictive_partials(X, y, t.family, self._stored_samples(what), rows=slice(1, None),
+                                         device=self.device)
 
     def posterior_predictive(self, X_new=None):
         """Posterior predictive mean and variance of a new observation at the rows X_new (n_eval, D)
@@ -422,8 +359,7 @@ class HMC_sampler(sampler):
 
     # ------------------------------------------------------------------ posterior quantiles
     def _stored_samples(self, what):
-        """The stored samples of the last run: q_chain_device where the run left it, else q_chain
-        (the source rule of _predictive_partials)."""
+        """The stored samples of the last run: q_chain_device where the run left it, else q_chain."""
         src = getattr(self, "q_chain_device", None)
         if src is None and getattr(self, "engine", None) is not None:
             src = self.q_chain
@@ -458,16 +394,7 @@ class HMC_sampler(sampler):
         if verbose:
             self.dt_total += elapsed
             print("Ran %d chains on %s: %.2f s" % (N, self.device, elapsed))
-        self.engine = eng
-        self.q_chain_device = eng.q_chain
-        self.q_device = eng.q
-        if eng.q_chain is not None:
-            self.q_chain = eng.q_chain.cpu().numpy()
-        else:
-            self.q_chain = None                     # streaming mode: statistics only
-        self.E_chain = eng.E_chain.cpu().numpy()[:, :, None]
-        self.dE_chain = eng.dE_chain.cpu().numpy()[:, :, None]
-        self._read_adapt(eng)
+        self._publish(eng)
         if eng.n_save:
             n_save = eng.n_save
             self.decision_chain = np.zeros((n_save + 1, 1), dtype=int)
@@ -476,9 +403,17 @@ class HMC_sampler(sampler):
             tl = eng.traj_len.cpu().numpy()
             self.phi_q = [T_[i, :tl[i]].copy() for i in range(n_save) if tl[i] > 0]
 
-    def _read_adapt(self, eng):
-        """step_scale, accept_stat_warm_up, accept_stat and adapt_state of a run through the _adapt
-        entries (include/hmc.h: hmc_adapt state slots); None otherwise."""
+    def _publish(self, eng):
+        """The run's results as the reference's NumPy attributes (q_chain None in streaming mode:
+        statistics only), the engine and its device arrays, and, of a run through the _adapt entries,
+        step_scale, accept_stat_warm_up, accept_stat and adapt_state (include/hmc.h: hmc_adapt state
+        slots; None otherwise)."""
+        self.engine = eng
+        self.q_chain_device = eng.q_chain
+        self.q_device = eng.q
+        self.q_chain = eng.q_chain.cpu().numpy() if eng.q_chain is not None else None
+        self.E_chain = eng.E_chain.cpu().numpy()[:, :, None]
+        self.dE_chain = eng.dE_chain.cpu().numpy()[:, :, None]
         st = getattr(eng, "adapt_state", None)
         if st is None:
             return
@@ -517,7 +452,7 @@ class HMC_sampler(sampler):
                           "draws)", UserWarning, stacklevel=2)
             rng, seed = "philox", int(np.random.randint(0, 2 ** 62, dtype=np.int64))
         # the target's own NUTS kernel (hmc_glm_nuts.hip) or the MVN kernels
-        engine = self._kernel_target[5] if self._kernel_target else NutsEngine
+        engine = self._kernel_target.nuts_engine if self._kernel_target else NutsEngine
         eng = engine(self.target(), self.Nchain, self.Niter, self.warm_up_num, self.thin_rate, self.d_max,
                      self.dt, cov_p=self.cov_p, rng=rng, seed=seed, fp_mode=self.fp_mode,
                      chain_offset=self.chain_offset, store_chain=self.store_chain, on_dmax=on_dmax,
@@ -547,13 +482,7 @@ class HMC_sampler(sampler):
         if verbose:
             self.dt_total += elapsed
             print("Ran %d NUTS chains on %s: %.2f s" % (N, self.device, elapsed))
-        self.engine = eng
-        self.q_chain_device = eng.q_chain
-        self.q_device = eng.q
-        self.q_chain = eng.q_chain.cpu().numpy() if eng.q_chain is not None else None
-        self.E_chain = eng.E_chain.cpu().numpy()[:, :, None]
-        self.dE_chain = eng.dE_chain.cpu().numpy()[:, :, None]
-        self._read_adapt(eng)
+        self._publish(eng)
         print("Compute acceptance rate: By default equal to 1.")                 # :800-805
         if self.warm_up_num > 0:
             self.accept_R_warm_up = 1.
@@ -568,20 +497,8 @@ class HMC_sampler(sampler):
         """samplers.py:831-839 for one (p, q) row or a batch of rows, on the GPU."""
         p = np.atleast_2d(np.asarray(p_old, dtype=np.float64))
         q = np.atleast_2d(np.asarray(q_old, dtype=np.float64))
-        T, K, keep = self._kernel_target_descriptors() if self._kernel_target else self._descriptors()
-        dev = self.device
-        pt, qt = _dev_tensor(p, dev), _dev_tensor(q, dev)
-        po, qo = torch.empty_like(pt), torch.empty_like(qt)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if self._kernel_target:
-            entry = self._kernel_target[3]
-            H.check(getattr(H.lib(), entry)(T, K, p.shape[0], H.ptr(pt), H.ptr(qt), H.ptr(po), H.ptr(qo), stream),
-                    entry)
-        else:
-            H.check(H.lib().hmc_leapfrog(T, K, p.shape[0], H.ptr(pt), H.ptr(qt), H.ptr(po), H.ptr(qo),
-                                         H.HMC_MODE_EXACT if self.fp_mode == "exact" else H.HMC_MODE_FAST,
-                                         stream), "hmc_leapfrog")
-        pn, qn = po.cpu().numpy(), qo.cpu().numpy()
+        mode = () if self._kernel_target else (H.HMC_MODE_EXACT if self.fp_mode == "exact" else H.HMC_MODE_FAST,)
+        pn, qn = self._row_call("leapfrog", [p, q], [p.shape, q.shape], extra=mode)
         if np.ndim(p_old) == 1:
             return pn[0], qn[0]
         return pn, qn
@@ -590,14 +507,7 @@ class HMC_sampler(sampler):
         """samplers.py:819-823 (V of utils.py:218 + K of :817) for one row or a batch."""
         qq = np.atleast_2d(np.asarray(q, dtype=np.float64))
         pp = np.atleast_2d(np.asarray(p, dtype=np.float64))
-        T, K, keep = self._kernel_target_descriptors() if self._kernel_target else self._descriptors()
-        dev = self.device
-        qt, pt = _dev_tensor(qq, dev), _dev_tensor(pp, dev)
-        Et = torch.empty(qq.shape[0], dtype=torch.float64, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        energy = getattr(H.lib(), self._kernel_target[4]) if self._kernel_target else H.lib().hmc_energy
-        H.check(energy(T, K, qq.shape[0], H.ptr(qt), H.ptr(pt), H.ptr(Et), stream), "hmc_energy")
-        E = Et.cpu().numpy()
+        E, = self._row_call("energy", [qq, pp], [qq.shape[:1]], what="hmc_energy")
         return E[0] if np.ndim(q) == 1 else E
 
     def K(self, p):
