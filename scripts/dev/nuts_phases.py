@@ -37,7 +37,7 @@ L = H.lib()
 L.hmc_debug_stamps.restype = ctypes.c_int64
 L.hmc_debug_stamps.argtypes = [ctypes.c_void_p, ctypes.c_int64]
 waves = min((N + 63) // 64, torch.cuda.get_device_properties(0).multi_processor_count) * 4
-W = 16                                             # kStampWords (hmc_internal.hpp)
+W = 16                                             # kStampWords (hmc_debug.hpp)
 buf = np.zeros(waves * W, dtype=np.uint64)
 got = L.hmc_debug_stamps(buf.ctypes.data, buf.size)
 ph = buf[:got].reshape(-1, W).astype(np.float64)

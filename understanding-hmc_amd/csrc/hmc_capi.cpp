@@ -12,6 +12,7 @@
 #include <unordered_map>
 
 #include "hmc.h"
+#include "hmc_debug.hpp"
 #include "hmc_internal.hpp"
 #include "hmc_logit.hpp"
 #include "hmc_mix.hpp"
@@ -21,10 +22,6 @@
 namespace {
 
 thread_local std::string g_err;
-#ifdef HMC_DEBUG_HOOKS
-unsigned long long* g_stamps = nullptr;   // HMC_DEBUG_STAMPS diagnostic buffer
-int64_t g_stamp_waves = 0;
-#endif
 
 hmc_status fail(hmc_status st, const char* fmt, ...) {
   char buf[512];
@@ -185,21 +182,7 @@ hmc::RandArgs rand_args(const hmc_target* t, const hmc_kinetic* k, const hmc_sch
   a.Ec = st->E_chain;
   a.dEc = st->dE_chain;
   a.cnt = st->counters;
-  a.dbgL = -1;
-#ifdef HMC_DEBUG_HOOKS
-  // Profiling experiments only: compiled into the separate debug build (make debug ->
-  // lib/libhmc_debug.so), never into the release libhmc.so the product and bench.py load.
-  if (const char* ab = getenv("HMC_DEBUG_ABLATE")) a.dbg = atoi(ab);
-  if (const char* dl = getenv("HMC_DEBUG_L")) a.dbgL = atoi(dl);
-  if (getenv("HMC_DEBUG_STAMPS")) {                                     // diagnostic phase timers
-    const int cpw = lay.cpw > 0 ? lay.cpw : 16;   // dense / NUTS layouts: 16 chains per wave
-    const int64_t waves = (s->n_chains + cpw - 1) / cpw;
-    if (g_stamps) (void)hipFree(g_stamps);
-    g_stamps = nullptr;
-    g_stamp_waves = waves;
-    if (hipMalloc(&g_stamps, waves * hmc::kStampWords * sizeof(unsigned long long)) == hipSuccess) a.stamps = g_stamps;
-  }
-#endif
+  hmc::apply_env(a, lay, s->n_chains);   // debug build only (hmc_debug.hpp)
   if (st->traj_q && st->traj_len && st->decision && st->n_save > 0) {
     a.traj_q = st->traj_q;
     a.traj_len = st->traj_len;
@@ -219,7 +202,7 @@ bool general_diag(const hmc_target* t, const hmc_kinetic* k) {
 hmc::RandArgs nuts_args(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
                         hmc_state* st, int D, void* workspace) {
   const bool replay = s->rng_mode == HMC_RNG_REPLAY;
-  const hmc::Layout lay{0, 0, 16, (D + 1) / 2};   // 16 chain slots per wave (debug stamps: one row per wave)
+  const hmc::Layout lay{0, 0, 16, (D + 1) / 2};   // 16 chain slots per wave
   hmc::RandArgs a = rand_args(t, k, s, replay ? r : nullptr, st, lay);
   a.d_max = s->d_max;
   a.on_dmax = s->on_dmax;
@@ -276,17 +259,6 @@ hmc_status view_too_large(const char* what) {
 }  // namespace
 
 extern "C" {
-
-#ifdef HMC_DEBUG_HOOKS
-// Diagnostic: copy the per-wave phase timers of the last HMC_DEBUG_STAMPS launch (debug build only).
-int64_t hmc_debug_stamps(unsigned long long* host, int64_t cap_words) {
-  if (!g_stamps) return 0;
-  const int64_t words = g_stamp_waves * hmc::kStampWords < cap_words ? g_stamp_waves * hmc::kStampWords : cap_words;
-  if (hipDeviceSynchronize() != hipSuccess) return 0;
-  if (hipMemcpy(host, g_stamps, words * sizeof(unsigned long long), hipMemcpyDeviceToHost) != hipSuccess) return 0;
-  return words;
-}
-#endif
 
 const char* hmc_version(void) { return "hmc_amd 0.1.0 gfx950 (diag random kernels, C ABI v1)"; }
 
@@ -386,7 +358,7 @@ hmc_status hmc_random_iters(const hmc_target* t, const hmc_kinetic* k, const hmc
   hmc::RandArgs a = rand_args(t, k, s, replay ? r : nullptr, st, lay);
   // the kernels keep per-launch tallies in 32 bits: Sum L^2 over one launch must stay < 2^31
   // (only very long trajectories, e.g. L_high = 200, with thousands of iterations split here)
-  const int64_t lmax = std::max<int64_t>(std::max(s->L_high, 1), a.dbgL > 0 ? a.dbgL : 1);
+  const int64_t lmax = std::max<int64_t>(std::max(s->L_high, 1), hmc::forced_L(a));
   const int64_t chunk = std::max<int64_t>(1, 0x7FFFFFFFll / (lmax * lmax));
   for (int it = s->iter_begin; it < s->iter_end;) {
     const int end = (int)std::min<int64_t>(s->iter_end, it + chunk);

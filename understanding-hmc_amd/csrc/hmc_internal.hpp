@@ -7,8 +7,6 @@
 
 namespace hmc {
 
-constexpr int kStampWords = 16;   // debug phase-timer words per wave (HMC_DEBUG_STAMPS)
-
 // Lane-group layout of one chain inside a wave64 (see hmc_device.hpp).
 struct Layout {
   int K;       // coordinate pairs per lane
@@ -56,14 +54,15 @@ struct RandArgs {
   double* ws;            // NUTS per-chain workspace (vectors: live points, boundaries, save slots)
   const double* tape;    // NUTS replay tape [n][tape_stride] (directions / uniforms in consumption order)
   int64_t tape_stride;
-  int dbg;               // ablation flags (HMC_DEBUG_ABLATE env; 0 in normal runs)
-  int dbgL;              // forced trajectory length (HMC_DEBUG_L env; -1 in normal runs)
-  unsigned long long* stamps;  // diagnostic phase timers (HMC_DEBUG_STAMPS env; null in normal runs),
-                               // kStampWords per wave
   const int32_t* order;  // dense: tile slot -> chain (L-ordered tiles) or null (slot = chain)
   double* gcache;        // dense: per-chain gradient at q [n][D] (in the order workspace) or null
   const int32_t* gvalid; // dense: nonzero once gcache holds the gradient of every chain's q
   int64_t ntiles;        // dense: 16-chain tiles
+#ifdef HMC_DEBUG_HOOKS   // debug build only, set by apply_env and read through hmc_debug.hpp
+  int dbg;               // ablation flags (HMC_DEBUG_ABLATE), or 0
+  int dbgL;              // forced trajectory length (HMC_DEBUG_L), or -1
+  unsigned long long* stamps;   // phase timers (HMC_DEBUG_STAMPS), kStampWords per wave, or null
+#endif
 };
 
 // Dense-precision (correlated MVN) kernels take the same argument block; `prec` is then the
@@ -107,6 +106,9 @@ bool leapfrog_three_term(const RandArgs& a, const Layout& lay, bool exact, bool 
 // that the dimension and the trajectory lengths decide, rows_kernel the whole of it for one launch.
 bool rows_shape(int D, int L_low, int L_high);
 bool rows_kernel(const RandArgs& a, const Layout& lay, bool exact, bool gen, bool replay);
+// Whether a launch takes the FULL instances of the iteration kernels (chain-0 capture and, in the
+// debug build, the hooks of hmc_debug.hpp) instead of the production ones.
+bool full_variant(const RandArgs& a);
 hipError_t launch_rows_iters(const RandArgs& a, hipStream_t s);
 hipError_t launch_dense_init(const DenseArgs& a, bool replay, hipStream_t s);
 hipError_t launch_dense_iters(const DenseArgs& a, bool exact, bool replay, hipStream_t s);

@@ -425,8 +425,8 @@ hipError_t launch(const MixArgs& m, const Layout& lay, int what, bool flag, hipS
 // on twice the lanes: with the gradient's component rows in flight a 16-pair instance does not fit
 // the register file.  choose_layout's scoring never picks 16 pairs for D <= 64
 // (tests/test_layout_query.py enumerates it) and the wave-per-chain shapes up to HMC_MIX_MAX_D take
-// at most 4, so only HMC_FORCE_K = 16 in the debug build reaches the remap.  Results do not depend
-// on the layout.
+// at most 4, so only HMC_FORCE_K = 16 in the debug build (hmc_debug.hpp) reaches the
+// remap.  Results do not depend on the layout.
 Layout mix_layout(int D, int L_low, int L_high) {
   Layout lay = choose_layout(D, L_low, L_high);
   if (lay.K == 16) {

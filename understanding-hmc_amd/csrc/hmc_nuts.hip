@@ -18,6 +18,7 @@
 // branch on the dimension.  All cross-lane reductions run in converged control flow.
 #include <algorithm>
 
+#include "hmc_debug.hpp"
 #include "hmc_dense_ops.hpp"
 #include "hmc_device.hpp"
 #include "hmc_internal.hpp"
@@ -101,27 +102,6 @@ inline uint64_t nuts_wait_cap(int64_t slots, int64_t n, int d_max, int kb) {
 enum : int { V_OLD_Q = 0, V_OLD_G = 1, V_NEW_Q = 2, V_NEW_G = 3, V_LEFT_Q = 4, V_LEFT_P = 5, V_LEFT_G = 6,
              V_RIGHT_Q = 7, V_RIGHT_P = 8, V_RIGHT_G = 9, V_SLOTS = 10 };
 static_assert(V_SLOTS == NutsTreeLayout::kFixedVecs, "the save slots follow the layout's fixed vectors");
-
-// Phase timers of the debug build (make debug; HMC_DEBUG_STAMPS): wave-uniform s_memtime deltas per
-// part of a wave step, summed over the launch: 0 transitions, 1 half kick + drift, 2 gradient
-// (MFMA), 3 half kick + energies, 4 new-point bookkeeping / saves, 5 loaded U-turn checks,
-// 6 progressive sampling, 7 sub-tree end; inside 0: 8 tree end (live point, row), 9 write-back +
-// drain + publish, 10 queue reservation, 11 poll + state loads, 12 momentum + tree start; 13 counts
-// the wave steps with a tree end.  The release library compiles none of it.
-// NUTS_TIMER(t, i) adds the time since timer t (t_ph: the parts of a step, t_sub: inside part 0) to
-// ph[i] and restarts it.
-#ifdef HMC_DEBUG_HOOKS
-#define NUTS_TIMER(t, i)                                        \
-  do {                                                          \
-    const unsigned long long t_ = __builtin_amdgcn_s_memtime(); \
-    ph[i] += t_ - t;                                            \
-    t = t_;                                                     \
-  } while (0)
-#else
-#define NUTS_TIMER(t, i) \
-  do {                   \
-  } while (0)
-#endif
 
 // Workspace (NutsTreeLayout::slots): per chain slot, nvec vectors of Dp = 4M doubles (dims, zero padded), slot-contiguous,
 // the 16 slots of a wave in one block addressed through a wave-uniform buffer descriptor (SGPR
@@ -323,10 +303,11 @@ void k_nuts_iters(RandArgs a) {
   int64_t tpos = 0;                                     // replay tape cursor (persists across launches)
   int old2 = 0;                                         // vector offset of the live_point_old pair
   unsigned long long n_lf = 0, n_unst = 0, n_dmax = 0, n_tape = 0, n_steps = 0, n_giveup = 0;
-#ifdef HMC_DEBUG_HOOKS
-  unsigned long long ph[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  unsigned long long t_ph = __builtin_amdgcn_s_memtime(), t_sub = t_ph;
-#endif
+  // debug build's phase timers (hmc_debug.hpp has the legend): clock t_ph times the parts of a wave
+  // step, t_sub the parts of the transitions; slot 13 counts the wave steps with a tree end
+  constexpr int t_ph = 0, t_sub = 1;
+  PhaseTimer<14, 2> tm(a);
+  tm.start(t_ph);
 
   auto draw = [&](bool direction) {                     // next random number of this chain (reference order)
     if constexpr (REPLAY) return NutsDraws::tape(tpos, a, n_tape, c, direction);
@@ -337,10 +318,8 @@ void k_nuts_iters(RandArgs a) {
     // ================= transitions (ITER_END -> ITER_START -> first doubling), converged reductions
     {
       const bool at_end = state == S_ITER_END;
-#ifdef HMC_DEBUG_HOOKS
-      t_sub = __builtin_amdgcn_s_memtime();
-      if (__builtin_amdgcn_ballot_w64(at_end)) ++ph[13];
-#endif
+      tm.start(t_sub);
+      if (tm.on() && __builtin_amdgcn_ballot_w64(at_end)) tm.count(13);
       if (at_end) {                                     // samplers.py:786-791: q = live_point_q_old
         vload<M, ME>(W, V_OLD_Q, old2, q);                  // its gradient: recomputed by the slot that
                                                         // takes the chain next (S_GRAD), so the live
@@ -362,7 +341,7 @@ void k_nuts_iters(RandArgs a) {
           state = S_FETCH;                              // hand the chain back after its unit
         }
       }
-      NUTS_TIMER(t_sub, 8);
+      tm.lap(8, t_sub);
       if (state == S_FETCH && live) {                   // tree done: write the chain's state through
 #pragma unroll
         for (int m = 0; m < ME; ++m) {
@@ -381,7 +360,7 @@ void k_nuts_iters(RandArgs a) {
           __hip_atomic_store(done + c, (unsigned)(it + 1 - a.it0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (state == S_FETCH) live = false;
       }
-      NUTS_TIMER(t_sub, 9);
+      tm.lap(9, t_sub);
       if (__builtin_amdgcn_ballot_w64(state == S_FETCH)) {   // next unit from the queue (converged shuffle;
         const bool fetching = state == S_FETCH;              // skipped in the steps where no slot fetches)
         unsigned long long u = (fetching && h == 0) ? atomicAdd(queue, 1ull) : 0ull;
@@ -410,7 +389,7 @@ void k_nuts_iters(RandArgs a) {
           }
         }
       }
-      NUTS_TIMER(t_sub, 10);
+      tm.lap(10, t_sub);
       if (state == S_WAIT) {                            // the chain's previous iteration published?
         const unsigned need = (unsigned)(it - a.it0);
         bool ready = need == 0;
@@ -437,7 +416,7 @@ void k_nuts_iters(RandArgs a) {
           state = S_GRAD;                               // gradient at q in the next wave step
         }
       }
-      NUTS_TIMER(t_sub, 11);
+      tm.lap(11, t_sub);
       const bool starting = state == S_ITER_START;
       double kin = 0.0;
       if (starting) {   // momentum (:565), dims h+4m, streamed to the boundaries: right = p, left = -p (:581-584)
@@ -526,10 +505,10 @@ void k_nuts_iters(RandArgs a) {
         k = 0;
         state = S_READY;
       }
-      NUTS_TIMER(t_sub, 12);
+      tm.lap(12, t_sub);
     }
     if (!__builtin_amdgcn_ballot_w64(state != S_DONE)) break;
-    NUTS_TIMER(t_ph, 0);
+    tm.lap(0, t_ph);
 
     // ================= one leapfrog for every chain inside a sub-tree (:612-614, :639)
     // chains outside a sub-tree are frozen by the EXEC mask of a divergent block (no per-dim
@@ -568,9 +547,9 @@ void k_nuts_iters(RandArgs a) {
         if ((m & 3) == 3) __builtin_amdgcn_sched_barrier(0);
       }
     }
-    NUTS_TIMER(t_ph, 1);
+    tm.lap(1, t_ph);
     gradient<MT, GEN, true, SHORT>(a, sP, lane, h, q, acc);
-    NUTS_TIMER(t_ph, 2);
+    tm.lap(2, t_ph);
     if (act) {
 #pragma unroll
       for (int m = 0; m < ME; ++m) {
@@ -623,7 +602,7 @@ void k_nuts_iters(RandArgs a) {
     }
     if (act && h == 0) ++n_lf;
     ++n_steps;
-    NUTS_TIMER(t_ph, 3);
+    tm.lap(3, t_ph);
 
     // ================= process the new point
     bool reject = false, sub_end = false;
@@ -648,7 +627,7 @@ void k_nuts_iters(RandArgs a) {
         vstore<M, ME>(W, V_SLOTS + 1, 2 * s, p);
       }
     }
-    NUTS_TIMER(t_ph, 4);
+    tm.lap(4, t_ph);
     // even point: sub-tree U-turn checks against check_points(mpt) (:699-736), converged loop
     const bool checking = later && !reject && (mpt & 1) == 0;
     {                                                   // the check against point mpt - 1, from registers
@@ -698,7 +677,7 @@ void k_nuts_iters(RandArgs a) {
         }                                               // (release, :735-736: nothing to free)
       }
     }
-    NUTS_TIMER(t_ph, 5);
+    tm.lap(5, t_ph);
     if (later && !reject) {                             // progressive sampling (:743-751)
       const auto w = TreeWeights::add_point(E_max_now, pi_new, E_tmp);
       E_max_now = w.E_max_now;
@@ -711,7 +690,7 @@ void k_nuts_iters(RandArgs a) {
       sub_end = k == Lsub;
     }
     if (act && reject) state = S_ITER_END;               // q = live_point_q_old (:649, :731)
-    NUTS_TIMER(t_ph, 6);
+    tm.lap(6, t_ph);
 
     // ================= sub-tree end: boundary, biased acceptance, termination (:757-784)
     // The other end (q, p, g) is loaded here for the termination dots; a next doubling towards it
@@ -775,14 +754,9 @@ void k_nuts_iters(RandArgs a) {
         state = S_READY;
       }
     }
-    NUTS_TIMER(t_ph, 7);
+    tm.lap(7, t_ph);
   }
-#ifdef HMC_DEBUG_HOOKS
-  if (a.stamps && lane == 0 && wv < n_waves) {   // g_stamps has one row per workspace wave
-#pragma unroll
-    for (int i = 0; i < 14; ++i) a.stamps[wv * kStampWords + i] = ph[i];
-  }
-#endif
+  if (tm.on() && lane == 0 && wv < n_waves) tm.store(wv);   // the stamp buffer has one row per workspace wave
 
   // counters (every chain's state was written back when its slot fetched the next one)
   n_lf = wave_sum_u64(n_lf);

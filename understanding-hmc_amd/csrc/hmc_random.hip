@@ -16,8 +16,7 @@
 // once per launch.  The arithmetic is fp64 VALU; EXACT mode keeps the reference's operation
 // order with no FMA contraction (built with -ffp-contract=off), so for diagonal targets the
 // sampled states are bit-identical to the NumPy reference on replayed streams.
-#include <cstdlib>
-
+#include "hmc_debug.hpp"
 #include "hmc_device.hpp"
 #include "hmc_internal.hpp"
 #include "hmc_lane_group.hpp"
@@ -27,10 +26,6 @@
 namespace hmc {
 
 namespace {
-
-__device__ __forceinline__ unsigned long long stamp(bool on) {
-  return on ? __builtin_amdgcn_s_memtime() : 0ull;
-}
 
 template <int K, bool GEN>
 __device__ __forceinline__ double chain_energy(const RandArgs& a, const Lane& ln, const int (&kk)[K],
@@ -72,7 +67,8 @@ __global__ __launch_bounds__(256) void k_random_init(RandArgs a) {
 // Iterations [it0, it1) (samplers.py:428-475).
 template <int K, bool EXACT, bool GEN, bool REPLAY>
 __global__ __launch_bounds__(256) void k_random_iters(RandArgs a) {
-  const unsigned long long t_start = stamp(a.stamps != nullptr);
+  PhaseTimer<6> tm(a);   // debug build's phase timers (hmc_debug.hpp has the legend)
+  const unsigned long long t_start = tm.now();
   const Lane ln = lane_info(a);
   const uint64_t gc = (uint64_t)(a.chain_offset + ln.c);
   int kk[K];
@@ -84,7 +80,6 @@ __global__ __launch_bounds__(256) void k_random_iters(RandArgs a) {
   RandomTally tally;
   int it_base = a.it0 - a.lpc, draw_L = 0;     // cached (L, log u) draws (Philox mode)
   double draw_lnu = 0.0;
-  unsigned long long ph[6] = {0, 0, 0, 0, 0, 0};   // diagnostic phase timers (stamps build path)
   // Retire the state loads here: the wait-count pass otherwise sees them pending at the loop
   // header and emits vmcnt(0) inside the loop, which (loads and stores share one in-order
   // counter on gfx950) stalls every iteration on the previous iteration's sample stores.
@@ -92,21 +87,20 @@ __global__ __launch_bounds__(256) void k_random_iters(RandArgs a) {
 
   for (int it = a.it0; it < a.it1; ++it) {
     // ---- momentum resample (samplers.py:431) and initial energy (:434)
-    const bool st_on = a.stamps != nullptr;
-    unsigned long long t_0 = stamp(st_on);
-    if (!(a.dbg & 1)) {
+    tm.start();
+    if (!ablate(a, kAblateMomentum)) {
       draw_momentum<K, GEN, REPLAY>(a, ln, it, kk, pv, p);
     } else {
 #pragma unroll
       for (int e = 0; e < 2 * K; ++e) p[e] = 0.3;
     }
-    unsigned long long t_1 = stamp(st_on);
-    const double E0 = (a.dbg & 2) ? 0.0 : chain_energy<K, GEN>(a, ln, kk, pv, q, p);
-    unsigned long long t_2 = stamp(st_on);
+    tm.lap(0);
+    const double E0 = ablate(a, kAblateEnergy) ? 0.0 : chain_energy<K, GEN>(a, ln, kk, pv, q, p);
+    tm.lap(1);
     const bool post = it >= a.wu;
     const bool write_row = stores_row(a, it);
     const int64_t row = row_of(a, it);
-    if (ln.leader && write_row && !(a.dbg & 8)) {       // :436-438 (Q14)
+    if (ln.leader && write_row && !ablate(a, kAblateRowStores)) {       // :436-438 (Q14)
       __builtin_nontemporal_store(E0, a.Ec + ln.c * (int64_t)a.Lc + row);
       __builtin_nontemporal_store(E0 - Eprev, a.dEc + ln.c * (int64_t)a.Lc + row);
     }
@@ -129,12 +123,12 @@ __global__ __launch_bounds__(256) void k_random_iters(RandArgs a) {
       }
       L = __shfl(draw_L, ln.base + (it - it_base), kWave);
       lnu = __shfl(draw_lnu, ln.base + (it - it_base), kWave);
-      if (a.dbg & 16) L = 12;
-      if (a.dbg & 4) L = 0;
+      if (ablate(a, kAblateL12)) L = 12;
+      if (ablate(a, kAblateZeroL)) L = 0;
       if (!ln.active) L = 0;
     }
 
-    unsigned long long t_3 = stamp(st_on);
+    tm.lap(2);
     // ---- chain-0 trajectory capture (samplers.py:442-452): lane holding dims 0,1 records q[:2]
     const bool cap = a.traj_q && (gc == 0) && (it <= a.n_save) && ln.leader;
     double* capp = cap ? a.traj_q + (int64_t)(it - 1) * a.traj_stride * 2 : nullptr;
@@ -200,48 +194,34 @@ __global__ __launch_bounds__(256) void k_random_iters(RandArgs a) {
       }
     }
 
-    unsigned long long t_4 = stamp(st_on);
+    tm.lap(3);
     // ---- final energy and Metropolis test (:455-472)
-    const double E1 = (a.dbg & 2) ? 0.0 : chain_energy<K, GEN>(a, ln, kk, pv, q, p);
-    unsigned long long t_5 = stamp(st_on);
+    const double E1 = ablate(a, kAblateEnergy) ? 0.0 : chain_energy<K, GEN>(a, ln, kk, pv, q, p);
+    tm.lap(4);
     const double dE = E1 - E0;
     const bool accept = (dE < 0.0) || (lnu < -dE);
     if (!accept) {
 #pragma unroll
       for (int e = 0; e < 2 * K; ++e) q[e] = qi[e];
     }
-    if (write_row && a.qc && !(a.dbg & 8) && row >= a.q_row0)
+    if (write_row && a.qc && !ablate(a, kAblateRowStores) && row >= a.q_row0)
       store_row<K>(a.qc + (ln.c * (int64_t)a.Lq + row % a.Lq) * a.D, a, kk, pv, q);
     if (cap) {
       a.traj_len[it - 1] = (L > 0 ? L : 0) + 1;
       a.decision[it - 1] = accept ? 1 : 0;
     }
     if (ln.leader) tally.count(a, it, post, accept, L);
-    if (st_on) {
-      const unsigned long long t_6 = stamp(true);
-      ph[0] += t_1 - t_0;   // momentum draw
-      ph[1] += t_2 - t_1;   // E0
-      ph[2] += t_3 - t_2;   // row bookkeeping + L/u draw
-      ph[3] += t_4 - t_3;   // leapfrog loop
-      ph[4] += t_5 - t_4;   // E1
-      ph[5] += t_6 - t_5;   // MH + stores
-    }
+    tm.lap(5);
   }
 
   // ---- state write-back and counters
   store_row<K>(a.q + ln.c * (int64_t)a.D, a, kk, pv, q);
   if (ln.leader) a.Eprev[ln.c] = Eprev;
-  if (a.stamps && ln.lane == 0) {
-    const int64_t wv = (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) a.stamps[wv * kStampWords + i] = ph[i];
-    a.stamps[wv * kStampWords + 6] = t_start;
-    a.stamps[wv * kStampWords + 7] = stamp(true);
-    // hardware placement: HW_ID (wave/simd/cu/sh/se) in the high word of slot 5's neighbour
-    const unsigned hwid = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-    const unsigned xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-    a.stamps[wv * kStampWords + 5] = ((unsigned long long)hwid << 32) | ((unsigned long long)(xcc & 0xffff) << 16) |
-                           (a.stamps[wv * kStampWords + 5] & 0xffffull);
+  if (tm.on() && ln.lane == 0) {
+    unsigned long long* row = tm.store((int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave));
+    row[6] = t_start;
+    row[7] = tm.now();
+    stamp_hw_id(row + 5);
   }
   tally.flush(a, ln.lane, (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave));
 }
@@ -294,14 +274,11 @@ static double expected_max(int lo, int hi, int c) {
 Layout choose_layout(int D, int L_low, int L_high) {
   static const int Ks[] = {1, 2, 4, 5, 8, 16};
   Layout best{0, 0, 0, (D + 1) / 2};
-#ifdef HMC_DEBUG_HOOKS
-  if (const char* fk = getenv("HMC_FORCE_K")) {   // experiments: force the pairs-per-lane template
-    const int K = atoi(fk);
+  if (const int K = force_K()) {   // debug build only: force the pairs-per-lane template
     const int lpc = (best.npairs + K - 1) / K;
     for (int k : Ks)
       if (k == K && lpc <= kWave) return Layout{K, lpc, kWave / lpc, best.npairs};
   }
-#endif
   // D > 64: one wavefront per chain (hmc_wave.hip): no trajectory-length divergence inside a
   // wave, wave-uniform control flow; K pairs per lane.
   if (best.npairs > kWave / 2) {
@@ -345,13 +322,7 @@ hipError_t launch_random_init(const RandArgs& a, const Layout& lay, bool gen, bo
 
 // The wave-per-chain kernels (hmc_wave.hip) serve this layout.
 bool wave_layout(const Layout& lay) {
-#ifdef HMC_DEBUG_HOOKS
-  const char* kern = getenv("HMC_KERNEL");       // experiments: "group" forces the lane-group kernel
-  const bool force_group = kern && kern[0] == 'g';
-#else
-  const bool force_group = false;
-#endif
-  return lay.cpw == 1 && !force_group && (lay.K == 1 || lay.K == 2 || lay.K == 4 || lay.K == 8 || lay.K == 16);
+  return lay.cpw == 1 && !force_group() && (lay.K == 1 || lay.K == 2 || lay.K == 4 || lay.K == 8 || lay.K == 16);
 }
 
 // Three-term leapfrog u[n+1] = (2 - (dt w)^2) u[n] - u[n-1] (hmc_wave.hip, TT): the momentum comes
@@ -386,6 +357,8 @@ bool leapfrog_three_term(const RandArgs& a, const Layout& lay, bool exact, bool 
 #endif
 }
 
+bool full_variant(const RandArgs& a) { return a.traj_q != nullptr || instrumented(a); }
+
 // Four chains per wavefront, one 16-lane row each (hmc_rows.hip): the shapes it is built for.  The
 // kernel packs L in 24 bits for its tallies and takes no empty trajectory.
 // -DHMC_NO_ROWS builds the library that never picks it (A/B).
@@ -402,8 +375,7 @@ bool rows_shape(int D, int L_low, int L_high) {
 // rows of the wave's four chains lie within a 32-bit byte offset of the first, and so do their rows
 // of the energy chains.
 bool rows_kernel(const RandArgs& a, const Layout& lay, bool exact, bool gen, bool replay) {
-  const bool full = a.traj_q != nullptr || a.dbg != 0 || a.dbgL >= 0;
-  if (replay || full || !rows_shape(a.D, a.L_low, a.L_high) || !leapfrog_three_term(a, lay, exact, gen)) return false;
+  if (replay || full_variant(a) || !rows_shape(a.D, a.L_low, a.L_high) || !leapfrog_three_term(a, lay, exact, gen)) return false;
   if ((a.Ec || a.dEc) && 4 * (int64_t)a.Lc * 8 >= (int64_t)1 << 31) return false;
   return !a.qc || 4 * (int64_t)a.Lq * a.D * 8 < (int64_t)1 << 31;
 }

@@ -14,6 +14,7 @@
 //   * E_chain / dE_chain values of up to 64 iterations are parked one per lane and written
 //     as one coalesced store (rows of a chain are contiguous).
 // HBM traffic per chain-iteration: one q_chain row (8D B) + E + dE (16 B).
+#include "hmc_debug.hpp"
 #include "hmc_device.hpp"
 #include "hmc_internal.hpp"
 #include "hmc_target_ops.hpp"
@@ -141,10 +142,11 @@ constexpr int kK1Block = 1024;
 // is the one the per-lane scheme draws (independent of launch splits and of the ring).
 constexpr int kRingPairs = 128;
 
-// FULL: chain-0 trajectory capture and the ablation/debug hooks compiled in.  The production
-// variant (FULL = false) drops them: their pointers and flags are live across the iteration loop
+// FULL: chain-0 trajectory capture and, in the debug build, the hooks of hmc_debug.hpp compiled in;
+// in the release library a FULL instance is the capture instance and nothing else.  The production
+// variant (FULL = false) drops both: their pointers and flags are live across the iteration loop
 // and pushed the SGPR demand past the 8-waves/SIMD budget (spills to VGPR lanes cost one
-// v_readlane/v_writelane VALU slot each, ~45 per iteration).
+// v_readlane/v_writelane VALU slot each, ~45 per iteration).  The host picks with full_variant.
 // ODD: D is odd (the ring zeroes the missing coordinate of the last pair); a template parameter so
 // that the common even-D kernel carries no per-pass test.
 // TT: the FAST identity-target leapfrog in its three-term (Störmer) form, one FMA per coordinate
@@ -152,11 +154,7 @@ constexpr int kRingPairs = 128;
 template <int K, bool EXACT, bool GEN, bool REPLAY, bool FULL, bool ODD = false, bool TT = false>
 __device__ __forceinline__ void wave_iters(const RandArgs& a) {
   static_assert(!TT || (!EXACT && !GEN), "the three-term leapfrog serves the FAST identity-target kernels only");
-#ifdef HMC_NO_RING
-  constexpr bool RING = false;
-#else
   constexpr bool RING = K == 1 && !REPLAY;
-#endif
   __shared__ double s_ntab[REPLAY ? 2 : kNormalTableDoubles];   // Box–Muller tables (Philox mode)
   // per wave: kRingPairs ring slots (2 KB, 2 KB-aligned: a slot's byte address is the wave's base
   // OR'd with 16 * slot)
@@ -291,7 +289,7 @@ __device__ __forceinline__ void wave_iters(const RandArgs& a) {
       if (dEc) __builtin_nontemporal_store(dE, dEc + row_first + lane);
     }
   };
-  const bool cap_chain = FULL && a.traj_q && gc == 0 && !(a.dbg & 32);
+  const bool cap_chain = FULL && a.traj_q && gc == 0 && !ablate(a, kAblateCapture);
   // per-launch tallies of one chain: (it1 - it0) <= 2^31 / L_high^2 is checked on the host, so
   // 32-bit counters cannot wrap (half the SGPRs of 64-bit ones)
   uint32_t n_acc = 0, n_acc_wu = 0, n_lf = 0, n_lf2 = 0, n_oob = 0;
@@ -361,7 +359,7 @@ __device__ __forceinline__ void wave_iters(const RandArgs& a) {
       L = __builtin_amdgcn_readlane(draw_L, it - it_base);
       lnu = readlane_d(draw_lnu, it - it_base);
     }
-    if (FULL && a.dbgL >= 0) L = a.dbgL;                          // diagnostics: forced trajectory length
+    if (FULL && forced_L(a) >= 0) L = forced_L(a);                // debug build: forced trajectory length
     L = uniform_i(L);
 
     // chain-0 trajectory capture (samplers.py:442-452)
@@ -525,7 +523,7 @@ __device__ __forceinline__ void wave_iters(const RandArgs& a) {
     const bool more = it + 1 < a.it1;
     double kn = 0.0;
     double (&pnext)[2 * K] = FASTID ? p : pn;
-    if (more && !(FULL && (a.dbg & 256))) {
+    if (more && !(FULL && ablate(a, kAblateNextDraw))) {
       if constexpr (RING) ring_momentum(it + 1, pnext);
       else wave_momentum<K, GEN, REPLAY>(a, c, gc, it + 1, kk, pv, pnext, s_ntab);
       if constexpr (!FASTID) kn = kin_partial<K, GEN>(a, kk, pv, pnext);
@@ -551,14 +549,12 @@ __device__ __forceinline__ void wave_iters(const RandArgs& a) {
       const double dE = E1 - E0;                          // samplers.py:459
       accept = (dE < 0.0) || (lnu < -dE);                 // :462
     }
-    if (!accept && !(FULL && (a.dbg & 128))) {
-#ifndef HMC_AB_SELECT
+    if (!accept && !(FULL && ablate(a, kAblateRestore))) {
       asm volatile("" ::: "memory");   // keep a (uniform) branch: no per-iteration selects on accept
-#endif
 #pragma unroll
       for (int e = 0; e < 2 * K; ++e) q[e] = qi[e];
     }
-    if (write_row && qcb && !(FULL && (a.dbg & 64)) && row >= a.q_row0) {
+    if (write_row && qcb && !(FULL && ablate(a, kAblateQStore)) && row >= a.q_row0) {
       double* rowp = qcb + (int64_t)qslot * a.D;
 #pragma unroll
       for (int j = 0; j < K; ++j)
@@ -598,9 +594,7 @@ __device__ __forceinline__ void wave_iters(const RandArgs& a) {
         E0 = 0.5 * (a.logc + (m0 + kn));
       } else {                                            // V(q_next) + K(p_next) in one reduction
         if (accept) {
-#ifndef HMC_AB_SELECT
           asm volatile("" ::: "memory");
-#endif
           m0l = m1l;
         }
         E0 = 0.5 * (a.logc + wave_sum_dpp(m0l + kn));
@@ -650,7 +644,7 @@ __global__ __launch_bounds__(kK1Block) __attribute__((amdgpu_waves_per_eu(8))) v
 
 template <int K, bool EXACT, bool GEN, bool REPLAY, bool TT>
 void launch_wave_one(const RandArgs& a, dim3 grid, hipStream_t s) {
-  const bool full = a.traj_q != nullptr || a.dbg != 0 || a.dbgL >= 0;
+  const bool full = full_variant(a);
   if constexpr (K == 1) {
     const dim3 g1((unsigned)((a.n + kK1Block / kWave - 1) / (kK1Block / kWave)));
     const bool odd = (a.D & 1) != 0 && !REPLAY;   // only the ring (Philox) path specialises on odd D
