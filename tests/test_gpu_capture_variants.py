@@ -1,6 +1,6 @@
 """Production instance against FULL instance of the Random iteration kernels.
 
-A launch with chain-0 capture takes the FULL instances (csrc/hmc_random.hip full_variant: the
+A launch with chain-0 capture takes the FULL instances (csrc/hmc_route.cpp full_variant: the
 lane-group kernel has one instance for both, hmc_wave.hip compiles the capture in only there); a
 launch without it takes the production ones.  The capture only records: the same seeded Philox run
 with and without it must leave the same bits in every output.

@@ -1,6 +1,6 @@
 """Host-side layout query (no GPU): hmc_random_layout answers which (K coordinate pairs per lane,
 lpc lanes per chain, cpw chains per wave) hmc_random_iters would launch
-(hmc_random.hip::choose_layout and wave_layout themselves, not a restatement).
+(hmc_route.cpp::choose_layout and wave_layout themselves, not a restatement).
 
 The table below is every layout the lane-group kernel (D <= 64) can take; the GPU cases of
 tests/test_gpu_lane_groups.py must reach each of them, so a change to the scoring that adds a layout
@@ -98,3 +98,29 @@ def test_gpu_cases_reach_every_layout():
         K, lpc, cpw, _ = layout(D, lo, hi)
         odd = [d for d in range(1, 65, 2) if layout(d, lo, hi)[:3] == (K, lpc, cpw)]
         assert D % 2 == 1 or not odd, (D, odd)
+
+
+def test_routes_are_the_recorded_ones():
+    """tests/golden/random_routes.json (scripts/dev/gen_random_routes.py, written from the library
+    of the commit before the kernel choice moved into csrc/hmc_route.cpp): layout, leapfrog form and
+    workspace sizes over a grid that crosses every edge of the choice, entry for entry."""
+    import importlib.util
+    import json
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("gen_random_routes",
+                                                  os.path.join(root, "scripts", "dev", "gen_random_routes.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(os.path.join(root, "tests", "golden", "random_routes.json")) as f:
+        want = json.load(f)["entries"]
+    assert len(want) == 862                   # a regenerated file cannot shrink unnoticed
+    got = gen.table()
+    assert [c for c, _ in got] == [c for c, _ in want]
+    bad = [(c, a, b) for (c, a), (_, b) in zip(got, want) if a != b]
+    assert not bad, (len(bad), bad[:5])
+    statuses = {a[0] for _, a in want}
+    layouts = {tuple(a[1:5]) for _, a in want if a[0] == 0}
+    # both sides of the three-term rule's length bound where m = 2 decides it (dt = 1.999: 199 | 200)
+    assert {c[3]: a[5] for c, a in want if c[0] == 129 and c[7] == 1.999} == {199: 1, 200: 0, 399: 0, 400: 0}
+    assert statuses == {0, 5} and (4, 16, 4, 0) in layouts and {a[5] for _, a in want} == {0, 1}

@@ -1,5 +1,5 @@
 """Host-side choice of the leapfrog form (no GPU): hmc_random_leapfrog_form answers what
-hmc_random_iters would launch (hmc_random.hip::leapfrog_three_term)."""
+hmc_random_iters would launch (hmc_route.cpp::leapfrog_three_term)."""
 import ctypes
 
 

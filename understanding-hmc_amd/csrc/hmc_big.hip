@@ -20,6 +20,7 @@
 // replay momenta are the reference's own N(0, cov_p) draws.  The energies then run in their own
 // wave-per-chain kernel after those products.
 #include "hmc_device.hpp"
+#include "hmc_dispatch.hpp"
 #include "hmc_internal.hpp"
 #include "hmc_dense_ops.hpp"
 #include "hmc_random_iter.hpp"
@@ -379,8 +380,6 @@ hipError_t mass_momentum(const BigArgs& b, bool replay, hipStream_t s) {
 
 }  // namespace
 
-bool big_path(int kind_dense, int D) { return kind_dense ? dense_tiles(D) == 0 : (D + 1) / 2 > 16 * kWave; }
-
 // vectors: p, qi; dense targets also g, gi and, with a full cov_p, its products kv, u
 static int big_vectors(bool dense, bool full_mass) { return dense ? (full_mass ? 6 : 4) : 2; }
 
@@ -421,19 +420,18 @@ hipError_t launch_big_init(const BigArgs& b, bool dense, bool replay, hipStream_
   if (dense)
     if (hipError_t e = grad_all(b, -1, s)) return e;
   const dim3 g = waves_grid(a.n);
-  if (a.minvf) {                                          // full cov_p: E after the products
-    if (replay) k_big_mass_p0<true><<<g, 256, 0, s>>>(b);
-    else k_big_mass_p0<false><<<g, 256, 0, s>>>(b);
-    if (hipError_t e = mass_momentum(b, replay, s)) return e;
-    k_big_energy<<<g, 256, 0, s>>>(b, 0);
-  } else if (dense) {
-    if (replay) k_big_init<true, true><<<g, 256, 0, s>>>(b);
-    else k_big_init<true, false><<<g, 256, 0, s>>>(b);
-  } else {
-    if (replay) k_big_init<false, true><<<g, 256, 0, s>>>(b);
-    else k_big_init<false, false><<<g, 256, 0, s>>>(b);
-  }
-  return hipGetLastError();
+  return with_bool(replay, [&](auto REPLAY) {
+    if (a.minvf) {                                        // full cov_p: E after the products
+      k_big_mass_p0<REPLAY()><<<g, 256, 0, s>>>(b);
+      if (hipError_t e = mass_momentum(b, replay, s)) return e;
+      k_big_energy<<<g, 256, 0, s>>>(b, 0);
+    } else if (dense) {
+      k_big_init<true, REPLAY()><<<g, 256, 0, s>>>(b);
+    } else {
+      k_big_init<false, REPLAY()><<<g, 256, 0, s>>>(b);
+    }
+    return hipGetLastError();
+  });
 }
 
 template <bool EXACT, bool DENSE>
@@ -443,16 +441,14 @@ hipError_t big_iterations(const BigArgs& b, bool replay, hipStream_t s) {
   const int lmax = a.L_high > 1 ? a.L_high - 1 : 0;       // L < L_high (randint, Q1)
   const bool mass = DENSE && a.minvf;
   for (int it = a.it0; it < a.it1; ++it) {
+    with_bool(replay, [&](auto REPLAY) {
+      if (mass) k_big_begin<DENSE, REPLAY(), true><<<gw, 256, 0, s>>>(b, it);
+      else k_big_begin<DENSE, REPLAY()><<<gw, 256, 0, s>>>(b, it);
+    });
     if (mass) {                                           // full cov_p: products, then E0
-      if (replay) k_big_begin<DENSE, true, true><<<gw, 256, 0, s>>>(b, it);
-      else k_big_begin<DENSE, false, true><<<gw, 256, 0, s>>>(b, it);
       if (hipError_t e = mass_momentum(b, replay, s)) return e;
       if (hipError_t e = gemm_all(b, BigGemm{a.minvf, b.g, false, b.kv}, -1, s)) return e;   // kick at q
       k_big_energy<<<gw, 256, 0, s>>>(b, it);
-    } else if (replay) {
-      k_big_begin<DENSE, true><<<gw, 256, 0, s>>>(b, it);
-    } else {
-      k_big_begin<DENSE, false><<<gw, 256, 0, s>>>(b, it);
     }
     for (int l = 0; l < lmax; ++l) {
       k_big_kick<EXACT, DENSE, true><<<ge, 256, 0, s>>>(b, l, it);
@@ -472,8 +468,9 @@ hipError_t big_iterations(const BigArgs& b, bool replay, hipStream_t s) {
 }
 
 hipError_t launch_big_iters(const BigArgs& b, bool dense, bool exact, bool replay, hipStream_t s) {
-  if (exact) return dense ? big_iterations<true, true>(b, replay, s) : big_iterations<true, false>(b, replay, s);
-  return dense ? big_iterations<false, true>(b, replay, s) : big_iterations<false, false>(b, replay, s);
+  return with_bool(exact, [&](auto EXACT) {
+    return with_bool(dense, [&](auto DENSE) { return big_iterations<EXACT(), DENSE()>(b, replay, s); });
+  });
 }
 
 }  // namespace hmc

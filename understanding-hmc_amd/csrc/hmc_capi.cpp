@@ -17,6 +17,7 @@
 #include "hmc_logit.hpp"
 #include "hmc_mix.hpp"
 #include "hmc_pred.hpp"
+#include "hmc_route.hpp"
 #include "hmc_select.hpp"
 
 namespace {
@@ -103,15 +104,6 @@ hmc_status check_chain_init(const hmc_target* t, const hmc_kinetic* k, const hmc
   return HMC_OK;
 }
 
-// The trajectory range a lane-group layout is chosen for at chain init: the schedule's, or the
-// reference's default (5, 20) when the caller left it unset (init draws no trajectory length).
-struct TrajRange {
-  int lo, hi;
-};
-TrajRange init_traj_range(const hmc_schedule* s) {
-  return s->L_high > s->L_low ? TrajRange{s->L_low, s->L_high} : TrajRange{5, 20};
-}
-
 // What the Random iteration entries (MVN, mixture, GLM) check alike once the target and the schedule
 // have passed, in the order the entries have always checked it.  *run: there is something to launch;
 // HMC_OK without it is the entry's answer (empty batch or empty iteration range).
@@ -168,7 +160,7 @@ hmc::RandArgs rand_args(const hmc_target* t, const hmc_kinetic* k, const hmc_sch
   a.minvf = k->minv_full;
   a.cholt = k->p_chol_t;
   a.kick = k->kick;
-  if (r) {
+  if (r && s->rng_mode == HMC_RNG_REPLAY) {   // Philox draws read no replay block
     a.rp0 = r->p0;
     a.rp = r->p;
     a.rlnu = r->lnu;
@@ -177,13 +169,13 @@ hmc::RandArgs rand_args(const hmc_target* t, const hmc_kinetic* k, const hmc_sch
   a.q = st->q;
   a.Eprev = st->E_prev;
   a.qc = st->q_chain;
-  a.Lq = st->qc_rows > 0 ? (int)st->qc_rows : s->L_chain;
+  a.Lq = hmc::window_rows(s, st);
   a.q_row0 = (int)st->qc_row0;
   a.Ec = st->E_chain;
   a.dEc = st->dE_chain;
   a.cnt = st->counters;
   hmc::apply_env(a, lay, s->n_chains);   // debug build only (hmc_debug.hpp)
-  if (st->traj_q && st->traj_len && st->decision && st->n_save > 0) {
+  if (hmc::captures_chain0(st)) {
     a.traj_q = st->traj_q;
     a.traj_len = st->traj_len;
     a.decision = st->decision;
@@ -193,17 +185,13 @@ hmc::RandArgs rand_args(const hmc_target* t, const hmc_kinetic* k, const hmc_sch
   return a;
 }
 
-bool general_diag(const hmc_target* t, const hmc_kinetic* k) {
-  return t->q0 || t->prec || k->minv || k->p_scale || k->dt_vec;
-}
-
 // rand_args plus what the NUTS kernels take: the tree's depth limit, the workspace, the replay tape;
 // no chain-0 capture (the reference never fills it for NUTS)
 hmc::RandArgs nuts_args(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
                         hmc_state* st, int D, void* workspace) {
   const bool replay = s->rng_mode == HMC_RNG_REPLAY;
   const hmc::Layout lay{0, 0, 16, (D + 1) / 2};   // 16 chain slots per wave
-  hmc::RandArgs a = rand_args(t, k, s, replay ? r : nullptr, st, lay);
+  hmc::RandArgs a = rand_args(t, k, s, r, st, lay);
   a.d_max = s->d_max;
   a.on_dmax = s->on_dmax;
   a.ws = static_cast<double*>(workspace);
@@ -242,12 +230,24 @@ hmc_status ws_check(const void* p, int64_t need, const char* what) {
   return HMC_OK;
 }
 
-// Bytes of hmc_state.order this Random-sampler call reads or writes (0: none).
-int64_t order_need(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, const hmc_state* st) {
-  if (!st->order || s->n_chains == 0) return 0;
-  const bool dense = t->kind == HMC_TARGET_DENSE;
-  if (hmc::big_path(dense, t->D)) return hmc::big_workspace_bytes(s->n_chains, t->D, dense, k->minv_full != nullptr);
-  return dense ? hmc::dense_workspace_bytes(s->n_chains, t->D) : 0;
+// What the sized Random entries (*_ws) do before the plain entry runs: the schedule's checks, then
+// state.order against what the call's route reads or writes of it, recorded for later calls.
+hmc_status check_order_bytes(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, const hmc_state* st,
+                             int64_t order_bytes, bool iters, const char* what) {
+  if (hmc_status e = check_schedule(t, k, s, iters)) return e;
+  if (!st) return fail(HMC_EINVAL, "null state");
+  const int64_t need = hmc::random_order_bytes(t, k, s, st);
+  if (order_bytes < need)
+    return fail(HMC_EINVAL, "%s: state.order of %lld bytes, this call needs %lld (hmc_random_workspace_size_ex)", what,
+                (long long)order_bytes, (long long)need);
+  if (st->order) ws_record(st->order, order_bytes);
+  return HMC_OK;
+}
+
+// The NUTS depth limit's range; status: HMC_EINVAL from the MVN entries, HMC_ENOTSUP from the GLM one.
+hmc_status check_d_max(const hmc_schedule* s, hmc_status status, const char* what) {
+  if (s->d_max >= 1 && s->d_max <= hmc::kNutsDmaxMax) return HMC_OK;
+  return fail(status, "%s: d_max=%d must be in [1, %d]", what, s->d_max, hmc::kNutsDmaxMax);
 }
 
 hmc_status view_too_large(const char* what) {
@@ -270,20 +270,17 @@ hmc_status hmc_chain_init(const hmc_target* t, const hmc_kinetic* k, const hmc_s
   bool run;
   if (hmc_status e = check_chain_init(t, k, s, r, q_start, st, &run); e != HMC_OK || !run) return e;
   const bool replay = s->rng_mode == HMC_RNG_REPLAY;
-  if (hmc_status e = ws_check(st->order, order_need(t, k, s, st), "hmc_chain_init: state.order")) return e;
-  const bool dense = t->kind == HMC_TARGET_DENSE;
-  if (hmc::big_path(dense, t->D)) {   // large D: chain state in the workspace (hmc_big.hip)
+  const hmc::RandomRoute route = hmc::random_route(t, k, s, st, true);
+  if (hmc_status e = ws_check(st->order, route.order_bytes, "hmc_chain_init: state.order")) return e;
+  hmc::RandArgs a = rand_args(t, k, s, r, st, route.lay);
+  a.qstart = q_start;
+  if (route.kernel == hmc::RandomKernel::Big) {   // chain state in the workspace (hmc_big.hip)
     if (!st->order) return fail(HMC_EINVAL, "D=%d needs hmc_random_workspace_size() bytes in state.order", t->D);
-    const hmc::Layout lay{0, 0, 0, (t->D + 1) / 2};
-    hmc::RandArgs a = rand_args(t, k, s, replay ? r : nullptr, st, lay);
-    a.qstart = q_start;
+    const bool dense = t->kind == HMC_TARGET_DENSE;
     return hip_status(hmc::launch_big_init(hmc::big_args(a, st->order, dense), dense, replay, (hipStream_t)stream),
                       "hmc_chain_init(large D)");
   }
-  if (t->kind == HMC_TARGET_DENSE) {
-    const hmc::Layout lay{0, 0, 0, (t->D + 1) / 2};
-    hmc::RandArgs a = rand_args(t, k, s, replay ? r : nullptr, st, lay);
-    a.qstart = q_start;
+  if (route.kernel == hmc::RandomKernel::Dense) {
     if (st->order) {   // the gradient cache no longer matches q: the next launch recomputes it
       int32_t* valid = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(st->order) +
                                                   hmc::dense_gcache_offset_bytes(s->n_chains) - 16);
@@ -292,13 +289,7 @@ hmc_status hmc_chain_init(const hmc_target* t, const hmc_kinetic* k, const hmc_s
     }
     return hip_status(hmc::launch_dense_init(a, replay, (hipStream_t)stream), "hmc_chain_init(dense)");
   }
-  const TrajRange L = init_traj_range(s);
-  const hmc::Layout lay = hmc::choose_layout(t->D, L.lo, L.hi);
-  if (lay.K == 0) return fail(HMC_ENOTSUP, "D=%d too large for the diagonal kernels", t->D);
-  hmc::RandArgs a = rand_args(t, k, s, replay ? r : nullptr, st, lay);
-  a.qstart = q_start;
-  return hip_status(hmc::launch_random_init(a, lay, general_diag(t, k), replay, (hipStream_t)stream),
-                    "hmc_chain_init");
+  return hip_status(hmc::launch_random_init(a, route, replay, (hipStream_t)stream), "hmc_chain_init");
 }
 
 hmc_status hmc_random_iters(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
@@ -307,20 +298,18 @@ hmc_status hmc_random_iters(const hmc_target* t, const hmc_kinetic* k, const hmc
   bool run;
   if (hmc_status e = check_random_iters(t, k, s, r, st, &run); e != HMC_OK || !run) return e;
   const bool replay = s->rng_mode == HMC_RNG_REPLAY;
-  if (hmc_status e = ws_check(st->order, order_need(t, k, s, st), "hmc_random_iters: state.order")) return e;
-  const bool dense = t->kind == HMC_TARGET_DENSE;
-  if (hmc::big_path(dense, t->D)) {   // large D (hmc_big.hip)
+  const bool exact = s->fp_mode == HMC_MODE_EXACT;
+  const hmc::RandomRoute route = hmc::random_route(t, k, s, st, false);
+  if (hmc_status e = ws_check(st->order, route.order_bytes, "hmc_random_iters: state.order")) return e;
+  hmc::RandArgs a = rand_args(t, k, s, r, st, route.lay);
+  if (route.kernel == hmc::RandomKernel::Big) {   // chain state in the workspace (hmc_big.hip)
     if (!st->order) return fail(HMC_EINVAL, "D=%d needs hmc_random_workspace_size() bytes in state.order", t->D);
-    const hmc::Layout lay{0, 0, 0, (t->D + 1) / 2};
-    hmc::RandArgs a = rand_args(t, k, s, replay ? r : nullptr, st, lay);
-    return hip_status(hmc::launch_big_iters(hmc::big_args(a, st->order, dense), dense,
-                                            s->fp_mode == HMC_MODE_EXACT, replay, (hipStream_t)stream),
+    const bool dense = t->kind == HMC_TARGET_DENSE;
+    return hip_status(hmc::launch_big_iters(hmc::big_args(a, st->order, dense), dense, exact, replay,
+                                            (hipStream_t)stream),
                       "hmc_random_iters(large D)");
   }
-  if (t->kind == HMC_TARGET_DENSE) {
-    const hmc::Layout lay{0, 0, 0, (t->D + 1) / 2};
-    hmc::RandArgs a = rand_args(t, k, s, replay ? r : nullptr, st, lay);
-    const bool exact = s->fp_mode == HMC_MODE_EXACT;
+  if (route.kernel == hmc::RandomKernel::Dense) {
     int32_t* gvalid = nullptr;
     if (st->order) {   // gradient cache in the workspace (hmc_random_workspace_size)
       char* base = reinterpret_cast<char*>(st->order);
@@ -353,9 +342,6 @@ hmc_status hmc_random_iters(const hmc_target* t, const hmc_kinetic* k, const hmc
     }
     return HMC_OK;
   }
-  const hmc::Layout lay = hmc::choose_layout(t->D, s->L_low, s->L_high);
-  if (lay.K == 0) return fail(HMC_ENOTSUP, "D=%d too large for the diagonal kernels", t->D);
-  hmc::RandArgs a = rand_args(t, k, s, replay ? r : nullptr, st, lay);
   // the kernels keep per-launch tallies in 32 bits: Sum L^2 over one launch must stay < 2^31
   // (only very long trajectories, e.g. L_high = 200, with thousands of iterations split here)
   const int64_t lmax = std::max<int64_t>(std::max(s->L_high, 1), hmc::forced_L(a));
@@ -364,8 +350,7 @@ hmc_status hmc_random_iters(const hmc_target* t, const hmc_kinetic* k, const hmc
     const int end = (int)std::min<int64_t>(s->iter_end, it + chunk);
     a.it0 = it;
     a.it1 = end;
-    if (hmc_status e = hip_status(hmc::launch_random_iters(a, lay, s->fp_mode == HMC_MODE_EXACT, general_diag(t, k),
-                                                           replay, (hipStream_t)stream),
+    if (hmc_status e = hip_status(hmc::launch_random_iters(a, route, exact, replay, (hipStream_t)stream),
                                   "hmc_random_iters"))
       return e;
     it = end;
@@ -374,13 +359,8 @@ hmc_status hmc_random_iters(const hmc_target* t, const hmc_kinetic* k, const hmc
 }
 
 int32_t hmc_random_leapfrog_form(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s) {
-  if (!t || !k || !s || t->D < 1 || t->kind == HMC_TARGET_DENSE || hmc::big_path(false, t->D)) return 0;
-  const hmc::Layout lay = hmc::choose_layout(t->D, s->L_low, s->L_high);
-  if (lay.K == 0) return 0;
-  hmc::RandArgs a{};
-  a.dt = k->dt;
-  a.L_high = s->L_high;
-  return hmc::leapfrog_three_term(a, lay, s->fp_mode == HMC_MODE_EXACT, general_diag(t, k)) ? 1 : 0;
+  if (!t || !k || !s || t->D < 1) return 0;
+  return hmc::random_route(t, k, s, nullptr, false).three_term ? 1 : 0;   // false on the dense and large-D paths
 }
 
 hmc_status hmc_random_layout(const hmc_target* t, const hmc_schedule* s, int32_t out[4]) {
@@ -392,42 +372,22 @@ hmc_status hmc_random_layout_ex(const hmc_target* t, const hmc_kinetic* k, const
   if (t->D < 1) return fail(HMC_EINVAL, "D must be >= 1");
   if (s->L_high <= s->L_low) return fail(HMC_EINVAL, "L_low must be < L_high (randint)");
   if (t->kind == HMC_TARGET_DENSE) return fail(HMC_ENOTSUP, "hmc_random_layout: dense targets have no such layout");
-  if (hmc::big_path(false, t->D)) return fail(HMC_ENOTSUP, "hmc_random_layout: D=%d runs the large-D path", t->D);
-  const hmc::Layout lay = hmc::choose_layout(t->D, s->L_low, s->L_high);
-  if (lay.K == 0) return fail(HMC_ENOTSUP, "D=%d too large for the diagonal kernels", t->D);
-  // 97 <= D <= 112, FAST, Philox, identity target: the four-chains-per-wave kernel (hmc_rows.hip)
-  // takes the production launches (identity mass, scalar dt in the three-term range, no capture):
-  // 16 lanes per chain with 7 coordinates each, reported as ceil(7 / 2) pairs per lane.  With a
-  // kinetic descriptor the mass and the three-term rule (dt against L_high) are checked as the
-  // launch checks them; without one they are taken as met.
-  bool rows = hmc::rows_shape(t->D, s->L_low, s->L_high) && s->fp_mode != HMC_MODE_EXACT &&
-              s->rng_mode != HMC_RNG_REPLAY && !t->q0 && !t->prec;
-  if (rows && k) {
-    hmc::RandArgs a{};
-    a.dt = k->dt;
-    a.L_high = s->L_high;
-    rows = hmc::leapfrog_three_term(a, lay, false, general_diag(t, k));
-  }
-  if (rows) {
-    out[0] = 4;
-    out[1] = 16;
-    out[2] = 4;
-    out[3] = 0;
-    return HMC_OK;
-  }
-  out[0] = lay.K;
-  out[1] = lay.lpc;
-  out[2] = lay.cpw;
-  out[3] = hmc::wave_layout(lay) ? 1 : 0;
+  // the route of a production launch (no capture); without a kinetic descriptor the mass and the
+  // three-term rule, which the four-chain kernel needs, are taken as met
+  const hmc::RandomRoute route = hmc::random_route(t, k, s, nullptr, false);
+  if (route.kernel == hmc::RandomKernel::Big)
+    return fail(HMC_ENOTSUP, "hmc_random_layout: D=%d runs the large-D path", t->D);
+  // the four-chain kernel reports 16 lanes per chain with 7 coordinates each as ceil(7 / 2) pairs per lane
+  out[0] = route.lay.K;
+  out[1] = route.lay.lpc;
+  out[2] = route.lay.cpw;
+  out[3] = route.kernel == hmc::RandomKernel::Wave ? 1 : 0;
   return HMC_OK;
 }
 
 int64_t hmc_random_workspace_size_ex(const hmc_target* t, const hmc_kinetic* k, int64_t n_chains) {
   if (!t || n_chains < 0 || t->D < 1) return 0;
-  const bool dense = t->kind == HMC_TARGET_DENSE;
-  if (hmc::big_path(dense, t->D)) return hmc::big_workspace_bytes(n_chains, t->D, dense, !k || k->minv_full);
-  if (!dense) return 0;
-  return hmc::dense_workspace_bytes(n_chains, t->D);
+  return hmc::random_workspace_bytes(t, k, n_chains);
 }
 
 int64_t hmc_random_workspace_size(const hmc_target* t, int64_t n_chains) {
@@ -475,65 +435,35 @@ hmc_status hmc_workspace_register(const void* workspace, int64_t bytes) {
 
 hmc_status hmc_chain_init_ws(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
                              const double* q_start, hmc_state* st, int64_t order_bytes, void* stream) {
-  if (hmc_status e = check_schedule(t, k, s, false)) return e;
-  if (!st) return fail(HMC_EINVAL, "null state");
-  if (!k) return fail(HMC_EINVAL, "null kinetic");
-  const int64_t need = order_need(t, k, s, st);
-  if (order_bytes < need)
-    return fail(HMC_EINVAL, "hmc_chain_init_ws: state.order of %lld bytes, this call needs %lld "
-                "(hmc_random_workspace_size_ex)", (long long)order_bytes, (long long)need);
-  if (st->order) ws_record(st->order, order_bytes);
+  if (hmc_status e = check_order_bytes(t, k, s, st, order_bytes, false, "hmc_chain_init_ws")) return e;
   return hmc_chain_init(t, k, s, r, q_start, st, stream);
 }
 
 hmc_status hmc_random_iters_ws(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
                                hmc_state* st, int64_t order_bytes, void* stream) {
-  if (hmc_status e = check_schedule(t, k, s, true)) return e;
-  if (!st) return fail(HMC_EINVAL, "null state");
-  if (!k) return fail(HMC_EINVAL, "null kinetic");
-  const int64_t need = order_need(t, k, s, st);
-  if (order_bytes < need)
-    return fail(HMC_EINVAL, "hmc_random_iters_ws: state.order of %lld bytes, this call needs %lld "
-                "(hmc_random_workspace_size_ex)", (long long)order_bytes, (long long)need);
-  if (st->order) ws_record(st->order, order_bytes);
+  if (hmc_status e = check_order_bytes(t, k, s, st, order_bytes, true, "hmc_random_iters_ws")) return e;
   return hmc_random_iters(t, k, s, r, st, stream);
 }
 
-hmc_status hmc_nuts_iters_ws(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
-                             hmc_state* st, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (hmc_status e = check_schedule(t, k, s, false)) return e;   // also rejects a NULL k
-  if (s->d_max < 1 || s->d_max > hmc::kNutsDmaxMax) return fail(HMC_EINVAL, "d_max must be in [1, %d]", hmc::kNutsDmaxMax);
-  const int64_t need = nuts_need(t, k, s);
-  if (need < 0) return fail(HMC_EINVAL, "NUTS workspace: unsupported D=%d / d_max=%d", t->D, s->d_max);
-  if (workspace_bytes < need)
-    return fail(HMC_EINVAL, "NUTS workspace of %lld bytes; this call (D=%d, %lld chains, d_max=%d, %d iterations, "
-                "%s momenta) needs %lld (hmc_nuts_workspace_size_ex)", (long long)workspace_bytes, t->D,
-                (long long)s->n_chains, s->d_max, s->iter_end - s->iter_begin,
-                s->rng_mode == HMC_RNG_PHILOX && !k->minv_full ? "Philox" : "no pre-drawn", (long long)need);
-  ws_record(workspace, workspace_bytes);
-  return hmc_nuts_iters(t, k, s, r, st, workspace, stream);
-}
-
-hmc_status hmc_nuts_iters(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
-                          hmc_state* st, void* workspace, void* stream) {
-  if (hmc_status e = check_schedule(t, k, s, false)) return e;
+// hmc_nuts_iters once the schedule has passed; sized_need: nuts_need of this call where the sized
+// entry has computed it already, or NULL
+static hmc_status nuts_iters(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
+                             hmc_state* st, void* workspace, void* stream, const int64_t* sized_need) {
   if (!st) return fail(HMC_EINVAL, "null state");
   if (hmc_status e = check_window(t, s, st)) return e;
   if (hmc_status e = check_iter_range(s)) return e;
   if (s->n_chains == 0) return HMC_OK;   // empty batch: zero-size buffers may be NULL
   if (!st->q || !st->E_prev) return fail(HMC_EINVAL, "null state");
-  if (s->d_max < 1 || s->d_max > hmc::kNutsDmaxMax) return fail(HMC_EINVAL, "d_max must be in [1, %d]", hmc::kNutsDmaxMax);
+  if (hmc_status e = check_d_max(s, HMC_EINVAL, "hmc_nuts_iters")) return e;
   if (hmc_status e = check_mass(t, k, s)) return e;
   if (t->kind != HMC_TARGET_DENSE) return fail(HMC_ENOTSUP, "NUTS runs the dense kernel: pass prec as dense");
   const bool replay = s->rng_mode == HMC_RNG_REPLAY;
   if (replay && (!r || !r->p || !r->tape || r->tape_stride < 1)) return fail(HMC_EINVAL, "replay mode needs p and tape");
   if (s->n_chains == 0 || s->iter_end == s->iter_begin) return HMC_OK;
   if (!workspace) return fail(HMC_EINVAL, "null workspace");
-  {
-    const int64_t need = nuts_need(t, k, s);
-    if (need < 0) return fail(HMC_EINVAL, "NUTS workspace: unsupported D=%d / d_max=%d", t->D, s->d_max);
-    if (hmc_status e = ws_check(workspace, need, "hmc_nuts_iters: workspace")) return e;
-  }
+  const int64_t need = sized_need ? *sized_need : nuts_need(t, k, s);
+  if (need < 0) return fail(HMC_EINVAL, "NUTS workspace: unsupported D=%d / d_max=%d", t->D, s->d_max);
+  if (hmc_status e = ws_check(workspace, need, "hmc_nuts_iters: workspace")) return e;
   const hmc::RandArgs a = nuts_args(t, k, s, r, st, t->D, workspace);
   const bool exact = s->fp_mode == HMC_MODE_EXACT;
   switch (hmc::nuts_kernel(t->D)) {
@@ -545,6 +475,27 @@ hmc_status hmc_nuts_iters(const hmc_target* t, const hmc_kinetic* k, const hmc_s
       break;
   }
   return hip_status(hmc::launch_nuts_iters(a, exact, replay, (hipStream_t)stream), "hmc_nuts_iters");
+}
+
+hmc_status hmc_nuts_iters_ws(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
+                             hmc_state* st, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (hmc_status e = check_schedule(t, k, s, false)) return e;   // also rejects a NULL k
+  if (hmc_status e = check_d_max(s, HMC_EINVAL, "hmc_nuts_iters_ws")) return e;
+  const int64_t need = nuts_need(t, k, s);
+  if (need < 0) return fail(HMC_EINVAL, "NUTS workspace: unsupported D=%d / d_max=%d", t->D, s->d_max);
+  if (workspace_bytes < need)
+    return fail(HMC_EINVAL, "NUTS workspace of %lld bytes; this call (D=%d, %lld chains, d_max=%d, %d iterations, "
+                "%s momenta) needs %lld (hmc_nuts_workspace_size_ex)", (long long)workspace_bytes, t->D,
+                (long long)s->n_chains, s->d_max, s->iter_end - s->iter_begin,
+                s->rng_mode == HMC_RNG_PHILOX && !k->minv_full ? "Philox" : "no pre-drawn", (long long)need);
+  ws_record(workspace, workspace_bytes);
+  return nuts_iters(t, k, s, r, st, workspace, stream, &need);
+}
+
+hmc_status hmc_nuts_iters(const hmc_target* t, const hmc_kinetic* k, const hmc_schedule* s, const hmc_replay* r,
+                          hmc_state* st, void* workspace, void* stream) {
+  if (hmc_status e = check_schedule(t, k, s, false)) return e;
+  return nuts_iters(t, k, s, r, st, workspace, stream, nullptr);
 }
 
 hmc_status hmc_leapfrog(const hmc_target* t, const hmc_kinetic* k, int64_t n, const double* p, const double* q,
@@ -646,10 +597,10 @@ hmc_status hmc_mix_chain_init(const hmc_mixture* m, const hmc_kinetic* k, const 
   bool run;
   if (hmc_status e = check_chain_init(&t, k, s, r, q_start, st, &run); e != HMC_OK || !run) return e;
   const bool replay = s->rng_mode == HMC_RNG_REPLAY;
-  const TrajRange L = init_traj_range(s);
+  const hmc::TrajRange L = hmc::init_traj_range(s);
   const hmc::Layout lay = hmc::mix_layout(m->D, L.lo, L.hi);
   if (lay.K == 0) return fail(HMC_ENOTSUP, "D=%d too large for the mixture kernels", m->D);
-  hmc::RandArgs a = rand_args(&t, k, s, replay ? r : nullptr, st, lay);
+  hmc::RandArgs a = rand_args(&t, k, s, r, st, lay);
   a.qstart = q_start;
   return hip_status(hmc::launch_mix_init(mix_args(m, a), lay, replay, (hipStream_t)stream), "hmc_mix_chain_init");
 }
@@ -664,7 +615,7 @@ hmc_status hmc_mix_random_iters(const hmc_mixture* m, const hmc_kinetic* k, cons
   const bool replay = s->rng_mode == HMC_RNG_REPLAY;
   const hmc::Layout lay = hmc::mix_layout(m->D, s->L_low, s->L_high);
   if (lay.K == 0) return fail(HMC_ENOTSUP, "D=%d too large for the mixture kernels", m->D);
-  const hmc::RandArgs a = rand_args(&t, k, s, replay ? r : nullptr, st, lay);
+  const hmc::RandArgs a = rand_args(&t, k, s, r, st, lay);
   return hip_status(hmc::launch_mix_iters(mix_args(m, a), lay, replay, (hipStream_t)stream), "hmc_mix_random_iters");
 }
 
@@ -753,8 +704,8 @@ hmc_status glm_chain_init(const hmc_logistic* m, int family, const hmc_kinetic* 
   bool run;
   if (hmc_status e = check_chain_init(&t, k, s, r, q_start, st, &run); e != HMC_OK || !run) return e;
   const bool replay = s->rng_mode == HMC_RNG_REPLAY;
-  const hmc::Layout lay{0, 0, 0, (m->D + 1) / 2};
-  hmc::RandArgs a = rand_args(&t, k, s, replay ? r : nullptr, st, lay);
+  const hmc::Layout lay = hmc::flat_layout(m->D);
+  hmc::RandArgs a = rand_args(&t, k, s, r, st, lay);
   a.qstart = q_start;
   return hip_status(hmc::launch_logit_init(logit_args(m, a), family, replay, (hipStream_t)stream), what);
 }
@@ -780,8 +731,8 @@ hmc_status glm_random_iters(const hmc_logistic* m, int family, const hmc_kinetic
   bool run;
   if (hmc_status e = check_random_iters(&t, k, s, r, st, &run); e != HMC_OK || !run) return e;
   const bool replay = s->rng_mode == HMC_RNG_REPLAY;
-  const hmc::Layout lay{0, 0, 0, (m->D + 1) / 2};
-  const hmc::RandArgs a = rand_args(&t, k, s, replay ? r : nullptr, st, lay);
+  const hmc::Layout lay = hmc::flat_layout(m->D);
+  const hmc::RandArgs a = rand_args(&t, k, s, r, st, lay);
   return hip_status(hmc::launch_logit_iters(logit_args(m, a), family, replay, (hipStream_t)stream, ad), what);
 }
 
@@ -812,12 +763,33 @@ hmc_status glm_energy(const hmc_logistic* m, int family, const hmc_kinetic* k, i
   return hip_status(hmc::launch_logit_rows(x, family, false, (hipStream_t)stream), what);
 }
 
+hmc_status check_family(int family, const char* what) {
+  if (family == HMC_GLM_BERNOULLI || family == HMC_GLM_POISSON) return HMC_OK;
+  return fail(HMC_EINVAL, "%s: unknown family %d (HMC_GLM_BERNOULLI, HMC_GLM_POISSON)", what, family);
+}
+
 // hmc_glm -> the data descriptor the kernels take; HMC_EINVAL for a null descriptor or an unknown family
 hmc_status glm_data(const hmc_glm* m, const char* what, hmc_logistic* out) {
   if (!m) return fail(HMC_EINVAL, "%s: null glm target", what);
-  if (m->family != HMC_GLM_BERNOULLI && m->family != HMC_GLM_POISSON)
-    return fail(HMC_EINVAL, "%s: unknown family %d (HMC_GLM_BERNOULLI, HMC_GLM_POISSON)", what, m->family);
+  if (hmc_status e = check_family(m->family, what)) return e;
   *out = hmc_logistic{m->D, m->n, m->ldx, m->X, m->y, m->prior_prec};
+  return HMC_OK;
+}
+
+// A sample view's strides and row range (hmc_samples), and its row and sample counts.
+hmc_status check_view_rows(const hmc_samples* s, int32_t D, const char* what) {
+  if (s->row_stride < D) return fail(HMC_EINVAL, "%s: row_stride=%lld < D=%d", what, (long long)s->row_stride, D);
+  if (s->row_step < 1) return fail(HMC_EINVAL, "%s: row_step=%lld must be >= 1", what, (long long)s->row_step);
+  if (s->row_begin < 0 || s->row_end < s->row_begin || s->n_chains < 0)
+    return fail(HMC_EINVAL, "%s: rows [%lld, %lld) of %lld chains", what, (long long)s->row_begin,
+                (long long)s->row_end, (long long)s->n_chains);
+  return HMC_OK;
+}
+
+hmc_status view_counts(const hmc_samples* s, const char* what, int64_t* rows, int64_t* n_samples) {
+  *rows = (s->row_end - s->row_begin + s->row_step - 1) / s->row_step;
+  if (*rows > 0 && s->n_chains > INT64_MAX / *rows) return fail(HMC_EINVAL, "%s: chains x rows overflows", what);
+  *n_samples = s->n_chains * *rows;
   return HMC_OK;
 }
 
@@ -890,8 +862,7 @@ hmc_status glm_nuts_iters(const hmc_glm* m, const hmc_kinetic* k, const hmc_sche
   if (!st) return fail(HMC_EINVAL, "null state");
   if (hmc_status e = check_window(&t, s, st)) return e;
   if (hmc_status e = check_iter_range(s)) return e;
-  if (s->d_max < 1 || s->d_max > hmc::kNutsDmaxMax)
-    return fail(HMC_ENOTSUP, "%s: d_max=%d, the kernel takes 1 .. %d", what, s->d_max, hmc::kNutsDmaxMax);
+  if (hmc_status e = check_d_max(s, HMC_ENOTSUP, what)) return e;
   if (s->n_chains == 0) return HMC_OK;   // empty batch: zero-size buffers may be NULL
   if (!st->q || !st->E_prev) return fail(HMC_EINVAL, "null state");
   const bool replay = s->rng_mode == HMC_RNG_REPLAY;
@@ -951,23 +922,16 @@ hmc_status hmc_glm_predictive(const hmc_glm* eval, const hmc_samples* s, double*
   const char* what = "hmc_glm_predictive";
   if (!eval || !s) return fail(HMC_EINVAL, "%s: null evaluation set / sample set", what);
   if (!eval->X || !s->q || !out) return fail(HMC_EINVAL, "%s: null X, q or out", what);
-  if (eval->family != HMC_GLM_BERNOULLI && eval->family != HMC_GLM_POISSON)
-    return fail(HMC_EINVAL, "%s: unknown family %d (HMC_GLM_BERNOULLI, HMC_GLM_POISSON)", what, eval->family);
+  if (hmc_status e = check_family(eval->family, what)) return e;
   if (eval->D < 1 || eval->n < 0) return fail(HMC_EINVAL, "%s: D must be >= 1 and n >= 0", what);
   if (eval->ldx < eval->D) return fail(HMC_EINVAL, "%s: ldx=%lld < D=%d", what, (long long)eval->ldx, eval->D);
-  if (s->row_stride < eval->D)
-    return fail(HMC_EINVAL, "%s: row_stride=%lld < D=%d", what, (long long)s->row_stride, eval->D);
-  if (s->row_step < 1) return fail(HMC_EINVAL, "%s: row_step=%lld must be >= 1", what, (long long)s->row_step);
-  if (s->row_begin < 0 || s->row_end < s->row_begin || s->n_chains < 0)
-    return fail(HMC_EINVAL, "%s: rows [%lld, %lld) of %lld chains", what, (long long)s->row_begin,
-                (long long)s->row_end, (long long)s->n_chains);
+  if (hmc_status e = check_view_rows(s, eval->D, what)) return e;
   if (eval->D > HMC_LOGIT_MAX_D)
     return fail(HMC_ENOTSUP, "%s: D=%d, the kernel takes D <= %d", what, eval->D, HMC_LOGIT_MAX_D);
   if (eval->n > HMC_LOGIT_MAX_N)
     return fail(HMC_ENOTSUP, "%s: n=%d, the kernel takes n <= %d", what, eval->n, HMC_LOGIT_MAX_N);
-  const int64_t rows = (s->row_end - s->row_begin + s->row_step - 1) / s->row_step;
-  if (rows > 0 && s->n_chains > INT64_MAX / rows) return fail(HMC_EINVAL, "%s: chains x rows overflows", what);
-  const int64_t n_samples = s->n_chains * rows;
+  int64_t rows = 0, n_samples = 0;
+  if (hmc_status e = view_counts(s, what, &rows, &n_samples)) return e;
   if (eval->n == 0 || n_samples == 0) return HMC_OK;   // nothing to reduce: out stays as it is
   const int64_t need = hmc_glm_predictive_workspace_size(eval->D, eval->n, n_samples);
   if (!workspace) return fail(HMC_EINVAL, "%s: null workspace", what);
@@ -985,14 +949,8 @@ namespace {
 hmc_status select_view(const hmc_samples* s, int32_t D, const char* what, int64_t* rows, int64_t* n_samples) {
   if (!s) return fail(HMC_EINVAL, "%s: null sample set", what);
   if (D < 1) return fail(HMC_EINVAL, "%s: D must be >= 1", what);
-  if (s->row_stride < D) return fail(HMC_EINVAL, "%s: row_stride=%lld < D=%d", what, (long long)s->row_stride, D);
-  if (s->row_step < 1) return fail(HMC_EINVAL, "%s: row_step=%lld must be >= 1", what, (long long)s->row_step);
-  if (s->row_begin < 0 || s->row_end < s->row_begin || s->n_chains < 0)
-    return fail(HMC_EINVAL, "%s: rows [%lld, %lld) of %lld chains", what, (long long)s->row_begin,
-                (long long)s->row_end, (long long)s->n_chains);
-  *rows = (s->row_end - s->row_begin + s->row_step - 1) / s->row_step;
-  if (*rows > 0 && s->n_chains > INT64_MAX / *rows) return fail(HMC_EINVAL, "%s: chains x rows overflows", what);
-  *n_samples = s->n_chains * *rows;
+  if (hmc_status e = check_view_rows(s, D, what)) return e;
+  if (hmc_status e = view_counts(s, what, rows, n_samples)) return e;
   if (*n_samples > 0 && !s->q) return fail(HMC_EINVAL, "%s: null q", what);   // an empty view has no storage
   return HMC_OK;
 }

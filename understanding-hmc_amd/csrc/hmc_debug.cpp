@@ -10,12 +10,18 @@ namespace hmc {
 namespace {
 unsigned long long* g_stamps = nullptr;   // HMC_DEBUG_STAMPS buffer of the last launch's arguments
 int64_t g_stamp_waves = 0;
+
+int env_int(const char* name, int unset) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : unset;
+}
 }  // namespace
 
+bool instrumented() { return env_int("HMC_DEBUG_ABLATE", 0) != 0 || env_int("HMC_DEBUG_L", -1) >= 0; }
+
 void apply_env(RandArgs& a, const Layout& lay, int64_t n_chains) {
-  a.dbgL = -1;
-  if (const char* ab = getenv("HMC_DEBUG_ABLATE")) a.dbg = atoi(ab);
-  if (const char* dl = getenv("HMC_DEBUG_L")) a.dbgL = atoi(dl);
+  a.dbg = env_int("HMC_DEBUG_ABLATE", 0);
+  a.dbgL = env_int("HMC_DEBUG_L", -1);
   if (getenv("HMC_DEBUG_STAMPS")) {
     // one row per wave; the dense and NUTS argument blocks carry no lane-group layout and run 16
     // chain slots per wave
@@ -28,10 +34,7 @@ void apply_env(RandArgs& a, const Layout& lay, int64_t n_chains) {
   }
 }
 
-int force_K() {
-  const char* fk = getenv("HMC_FORCE_K");
-  return fk ? atoi(fk) : 0;
-}
+int force_K() { return env_int("HMC_FORCE_K", 0); }
 
 bool force_group() {
   const char* kern = getenv("HMC_KERNEL");

@@ -32,7 +32,7 @@ __device__ __forceinline__ bool ablate(const RandArgs& a, Ablate bit) { return (
 __host__ __device__ __forceinline__ int forced_L(const RandArgs& a) { return a.dbgL; }   // HMC_DEBUG_L, or -1
 __device__ __forceinline__ unsigned long long* stamps(const RandArgs& a) { return a.stamps; }
 
-inline bool instrumented(const RandArgs& a) { return a.dbg != 0 || a.dbgL >= 0; }
+bool instrumented();   // HMC_DEBUG_ABLATE or HMC_DEBUG_L set: the launch takes the FULL instances
 void apply_env(RandArgs& a, const Layout& lay, int64_t n_chains);   // the HMC_DEBUG_* variables into a
 int force_K();        // HMC_FORCE_K: the pairs-per-lane template to force (0: none)
 bool force_group();   // HMC_KERNEL=group: the lane-group kernel where the wave kernel would run
@@ -43,7 +43,7 @@ __device__ __forceinline__ constexpr bool ablate(const RandArgs&, Ablate) { retu
 __host__ __device__ __forceinline__ constexpr int forced_L(const RandArgs&) { return -1; }
 __device__ __forceinline__ constexpr unsigned long long* stamps(const RandArgs&) { return nullptr; }
 
-constexpr bool instrumented(const RandArgs&) { return false; }
+constexpr bool instrumented() { return false; }
 inline void apply_env(RandArgs&, const Layout&, int64_t) {}
 constexpr int force_K() { return 0; }
 constexpr bool force_group() { return false; }

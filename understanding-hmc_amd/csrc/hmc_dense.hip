@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "hmc_device.hpp"
+#include "hmc_dispatch.hpp"
 #include "hmc_internal.hpp"
 #include "hmc_dense_ops.hpp"
 #include "hmc_random_iter.hpp"
@@ -416,6 +417,7 @@ __global__ __launch_bounds__(256) void k_order_scatter(DenseArgs a, int it, bool
   if (c < a.n) order[base[bin] + rank] = (int32_t)c;
 }
 
+template <int S> using ShortForm = std::integral_constant<int, S>;
 
 template <int MT, bool EXACT, int WAVES>
 void launch_dense_w(const DenseArgs& a, bool gen, bool replay, hipStream_t s) {
@@ -423,37 +425,18 @@ void launch_dense_w(const DenseArgs& a, bool gen, bool replay, hipStream_t s) {
   const int64_t blocks = (a.ntiles + WAVES - 1) / WAVES;
   const dim3 grid((unsigned)std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)device_cus())));
   const size_t lds = (size_t)MT * 4 * MT * kWave * sizeof(double);
-  if (a.minvf) {
-    if (replay) k_dense_iters<MT, EXACT, true, true, WAVES, true><<<grid, 64 * WAVES, lds, s>>>(a);
-    else k_dense_iters<MT, EXACT, true, false, WAVES, true><<<grid, 64 * WAVES, lds, s>>>(a);
-  } else if (gen) {
-    if (replay) k_dense_iters<MT, EXACT, true, true, WAVES><<<grid, 64 * WAVES, lds, s>>>(a);
-    else k_dense_iters<MT, EXACT, true, false, WAVES><<<grid, 64 * WAVES, lds, s>>>(a);
-  } else {
-    bool done = false;
-    if constexpr (MT == 7) {
-      if (a.D <= 16 * (MT - 1) + 4) {                   // D = 97..100 (c3: D = 100)
-        if (replay) k_dense_iters<MT, EXACT, false, true, WAVES, false, kShortAlways><<<grid, 64 * WAVES, lds, s>>>(a);
-        else k_dense_iters<MT, EXACT, false, false, WAVES, false, kShortAlways><<<grid, 64 * WAVES, lds, s>>>(a);
-        done = true;
-      }
-    }
-    if (!done) {
-      if (replay) k_dense_iters<MT, EXACT, false, true, WAVES, false, kShortNever><<<grid, 64 * WAVES, lds, s>>>(a);
-      else k_dense_iters<MT, EXACT, false, false, WAVES, false, kShortNever><<<grid, 64 * WAVES, lds, s>>>(a);
-    }
-  }
-}
-
-template <int MT, bool EXACT>
-hipError_t launch_dense_mt2(const DenseArgs& a, bool gen, bool replay, hipStream_t s) {
-  launch_dense_w<MT, EXACT, HMC_DENSE_WAVES>(a, gen, replay, s);
-  return hipGetLastError();
-}
-
-template <int MT>
-hipError_t launch_dense_mt(const DenseArgs& a, bool exact, bool gen, bool replay, hipStream_t s) {
-  return exact ? launch_dense_mt2<MT, true>(a, gen, replay, s) : launch_dense_mt2<MT, false>(a, gen, replay, s);
+  // GEN, MASS and SHORT of one form; both its REPLAY instances
+  auto run = [&](auto GEN, auto MASS, auto SHORT) {
+    with_bool(replay, [&](auto REPLAY) {
+      k_dense_iters<MT, EXACT, GEN(), REPLAY(), WAVES, MASS(), SHORT()><<<grid, 64 * WAVES, lds, s>>>(a);
+    });
+  };
+  constexpr std::true_type Y;
+  constexpr std::false_type N;
+  if (a.minvf) run(Y, Y, ShortForm<kShortRuntime>{});
+  else if (gen) run(Y, N, ShortForm<kShortRuntime>{});
+  else if (MT != 7 || a.D > 16 * (MT - 1) + 4) run(N, N, ShortForm<kShortNever>{});
+  else if constexpr (MT == 7) run(N, N, ShortForm<kShortAlways>{});   // D = 97..100 (c3: D = 100)
 }
 
 }  // namespace
@@ -506,14 +489,12 @@ hipError_t launch_dense_order(const DenseArgs& a, int it, bool replay, int32_t* 
 
 hipError_t launch_dense_iters(const DenseArgs& a, bool exact, bool replay, hipStream_t s) {
   const bool gen = a.q0 || a.minv || a.pscale || a.dtv || a.minvf;
-  switch (dense_tiles(a.D)) {
-    case 1: return launch_dense_mt<1>(a, exact, gen, replay, s);
-    case 2: return launch_dense_mt<2>(a, exact, gen, replay, s);
-    case 4: return launch_dense_mt<4>(a, exact, gen, replay, s);
-    case 7: return launch_dense_mt<7>(a, exact, gen, replay, s);
-    case 8: return launch_dense_mt<8>(a, exact, gen, replay, s);
-  }
-  return hipErrorInvalidValue;
+  return with_value<1, 2, 4, 7, 8>(dense_tiles(a.D), [&](auto MT) {
+    return with_bool(exact, [&](auto EXACT) {
+      launch_dense_w<MT(), EXACT(), HMC_DENSE_WAVES>(a, gen, replay, s);
+      return hipGetLastError();
+    });
+  });
 }
 
 }  // namespace hmc

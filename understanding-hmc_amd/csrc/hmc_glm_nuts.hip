@@ -32,6 +32,7 @@
 // register's load or store is one contiguous 512-byte access of the wave (a chain-contiguous layout
 // would give 32-byte pieces).  nvec = 8 + 2 (d_max + 1): the two live points (their names swap on
 // acceptance), left q, p, g, right q, p, g, and d_max + 1 save slots of (q, p).  (GlmNutsLayout)
+#include "hmc_dispatch.hpp"
 #include "hmc_glm_ops.hpp"
 #include "hmc_nuts_layout.hpp"
 #include "hmc_nuts_tree.hpp"
@@ -349,15 +350,11 @@ hipError_t launch_mt(const LogitArgs& x0, bool replay, const hmc_adapt* ad, hipS
   LogitArgs x = x0;
   x.a.ntiles = GlmNutsLayout(x.a.n, MT, x.a.d_max).tiles;
   const dim3 grid((unsigned)((x.a.ntiles + kLogitWaves - 1) / kLogitWaves)), block(64 * kLogitWaves);
-  if (ad) {
-    const LogitAdaptArgs xa{x, *ad};
-    if (replay) k_glm_nuts<FAMILY, MT, true, true><<<grid, block, 0, s>>>(xa);
-    else k_glm_nuts<FAMILY, MT, false, true><<<grid, block, 0, s>>>(xa);
-  } else {
-    if (replay) k_glm_nuts<FAMILY, MT, true, false><<<grid, block, 0, s>>>(x);
-    else k_glm_nuts<FAMILY, MT, false, false><<<grid, block, 0, s>>>(x);
-  }
-  return hipGetLastError();
+  return with_bool(replay, [&](auto REPLAY) {
+    if (ad) k_glm_nuts<FAMILY, MT, REPLAY(), true><<<grid, block, 0, s>>>(LogitAdaptArgs{x, *ad});
+    else k_glm_nuts<FAMILY, MT, REPLAY(), false><<<grid, block, 0, s>>>(x);
+    return hipGetLastError();
+  });
 }
 
 // 16-dim tiles per chain of the instance that runs D: 1, 2, 4 or 8 (0: D out of range)
@@ -369,13 +366,7 @@ int glm_tiles(int D) {
 
 template <int FAMILY>
 hipError_t launch_family(const LogitArgs& x, bool replay, const hmc_adapt* ad, hipStream_t s) {
-  switch (glm_tiles(x.a.D)) {
-    case 1: return launch_mt<FAMILY, 1>(x, replay, ad, s);
-    case 2: return launch_mt<FAMILY, 2>(x, replay, ad, s);
-    case 4: return launch_mt<FAMILY, 4>(x, replay, ad, s);
-    case 8: return launch_mt<FAMILY, 8>(x, replay, ad, s);
-  }
-  return hipErrorInvalidValue;
+  return with_value<1, 2, 4, 8>(glm_tiles(x.a.D), [&](auto MT) { return launch_mt<FAMILY, MT()>(x, replay, ad, s); });
 }
 
 }  // namespace

@@ -90,25 +90,9 @@ inline NutsKernel nuts_kernel(int D) {
   return nuts_lock_path(D) ? NutsKernel::Lock : NutsKernel::PerChain;
 }
 
-Layout choose_layout(int D, int L_low, int L_high);
-bool wave_layout(const Layout& lay);   // launch_random_iters takes the wave-per-chain kernels (hmc_wave.hip)
-
-hipError_t launch_random_init(const RandArgs& a, const Layout& lay, bool gen, bool replay, hipStream_t s);
-hipError_t launch_random_iters(const RandArgs& a, const Layout& lay, bool exact, bool gen, bool replay,
-                               hipStream_t s);
-hipError_t launch_wave_iters(const RandArgs& a, int K, bool exact, bool gen, bool replay, bool three_term,
+// The diagonal-target iteration kernels behind launch_random_iters (hmc_route.hpp says which runs).
+hipError_t launch_wave_iters(const RandArgs& a, int K, bool exact, bool gen, bool replay, bool three_term, bool full,
                              hipStream_t s);
-// Whether launch_random_iters runs the FAST leapfrog in its three-term form (hmc_wave.hip, TT):
-// wave-per-chain layout, FAST mode, identity target and mass with a scalar dt inside the range
-// where recovering the momentum from the last two points is safe.
-bool leapfrog_three_term(const RandArgs& a, const Layout& lay, bool exact, bool gen);
-// Four chains per wavefront for 97 <= D <= 112 (hmc_rows.hip): rows_shape is the part of the choice
-// that the dimension and the trajectory lengths decide, rows_kernel the whole of it for one launch.
-bool rows_shape(int D, int L_low, int L_high);
-bool rows_kernel(const RandArgs& a, const Layout& lay, bool exact, bool gen, bool replay);
-// Whether a launch takes the FULL instances of the iteration kernels (chain-0 capture and, in the
-// debug build, the hooks of hmc_debug.hpp) instead of the production ones.
-bool full_variant(const RandArgs& a);
 hipError_t launch_rows_iters(const RandArgs& a, hipStream_t s);
 hipError_t launch_dense_init(const DenseArgs& a, bool replay, hipStream_t s);
 hipError_t launch_dense_iters(const DenseArgs& a, bool exact, bool replay, hipStream_t s);
@@ -136,7 +120,6 @@ struct BigArgs {
   double* lnu;   // [n] log u of the current iteration
   double* E0;    // [n] energy at the start of the current iteration
 };
-bool big_path(int kind_dense, int D);
 int64_t big_workspace_bytes(int64_t n, int D, bool dense, bool full_mass);
 BigArgs big_args(const RandArgs& a, void* ws, bool dense);
 hipError_t launch_big_init(const BigArgs& b, bool dense, bool replay, hipStream_t s);

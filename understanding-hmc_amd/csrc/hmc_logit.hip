@@ -40,6 +40,7 @@
 //
 // One arithmetic for both fp_mode values (fast_exp / fast_log of hmc_device.hpp are ~1 ulp fp64,
 // not bit-identical to NumPy's).  Built with -ffp-contract=off; the FMAs are explicit.
+#include "hmc_dispatch.hpp"
 #include "hmc_glm_ops.hpp"
 #include "hmc_random_iter.hpp"
 
@@ -231,31 +232,18 @@ __global__ __launch_bounds__(64 * kLogitWaves) void k_logit_rows(LogitArgs x) {
   }
 }
 
-// what: 0 init, 1 iterations (ad: NULL the plain kernel, otherwise its ADAPT form), 2 rows
+// what: 0 init, 1 iterations (ad: NULL the plain kernel, otherwise its ADAPT form), 2 rows;
+// flag: REPLAY, or LEAP for the rows
 template <int FAMILY, int MT>
 hipError_t launch_mt(const LogitArgs& x, int what, bool flag, const hmc_adapt* ad, hipStream_t s) {
   const dim3 grid((unsigned)((x.a.ntiles + kLogitWaves - 1) / kLogitWaves)), block(64 * kLogitWaves);
-  switch (what) {
-    case 0:
-      if (flag) k_logit_init<FAMILY, MT, true><<<grid, block, 0, s>>>(x);
-      else k_logit_init<FAMILY, MT, false><<<grid, block, 0, s>>>(x);
-      break;
-    case 1:
-      if (ad) {
-        const LogitAdaptArgs xa{x, *ad};
-        if (flag) k_logit_iters<FAMILY, MT, true, true><<<grid, block, 0, s>>>(xa);
-        else k_logit_iters<FAMILY, MT, false, true><<<grid, block, 0, s>>>(xa);
-      } else {
-        if (flag) k_logit_iters<FAMILY, MT, true, false><<<grid, block, 0, s>>>(x);
-        else k_logit_iters<FAMILY, MT, false, false><<<grid, block, 0, s>>>(x);
-      }
-      break;
-    default:
-      if (flag) k_logit_rows<FAMILY, MT, true><<<grid, block, 0, s>>>(x);
-      else k_logit_rows<FAMILY, MT, false><<<grid, block, 0, s>>>(x);
-      break;
-  }
-  return hipGetLastError();
+  return with_bool(flag, [&](auto FLAG) {
+    if (what == 0) k_logit_init<FAMILY, MT, FLAG()><<<grid, block, 0, s>>>(x);
+    else if (what != 1) k_logit_rows<FAMILY, MT, FLAG()><<<grid, block, 0, s>>>(x);
+    else if (ad) k_logit_iters<FAMILY, MT, FLAG(), true><<<grid, block, 0, s>>>(LogitAdaptArgs{x, *ad});
+    else k_logit_iters<FAMILY, MT, FLAG(), false><<<grid, block, 0, s>>>(x);
+    return hipGetLastError();
+  });
 }
 
 // 16-dim output tiles per chain: 1, 2, 4 or 8 (D <= HMC_LOGIT_MAX_D = 128).  An instance runs all

@@ -28,6 +28,7 @@
 // fast_log of hmc_device.hpp), which cannot be bit-identical to NumPy's, so there is no EXACT
 // instance.  Built with -ffp-contract=off; the FMAs are explicit.
 #include "hmc_device.hpp"
+#include "hmc_dispatch.hpp"
 #include "hmc_lane_group.hpp"
 #include "hmc_mix.hpp"
 #include "hmc_random_iter.hpp"
@@ -409,33 +410,10 @@ hipError_t launch_k(const MixArgs& m, int what, bool flag, hipStream_t s) {
 
 hipError_t launch(const MixArgs& m, const Layout& lay, int what, bool flag, hipStream_t s) {
   if (m.a.n == 0) return hipSuccess;
-  switch (lay.K) {
-    case 1: return launch_k<1>(m, what, flag, s);
-    case 2: return launch_k<2>(m, what, flag, s);
-    case 4: return launch_k<4>(m, what, flag, s);
-    case 5: return launch_k<5>(m, what, flag, s);
-    case 8: return launch_k<8>(m, what, flag, s);
-  }
-  return hipErrorInvalidValue;
+  return with_value<1, 2, 4, 5, 8>(lay.K, [&](auto K) { return launch_k<K()>(m, what, flag, s); });
 }
 
 }  // namespace
-
-// choose_layout's lane groups, except that 16 pairs per lane (two lanes per chain) become 8 pairs
-// on twice the lanes: with the gradient's component rows in flight a 16-pair instance does not fit
-// the register file.  choose_layout's scoring never picks 16 pairs for D <= 64
-// (tests/test_layout_query.py enumerates it) and the wave-per-chain shapes up to HMC_MIX_MAX_D take
-// at most 4, so only HMC_FORCE_K = 16 in the debug build (hmc_debug.hpp) reaches the
-// remap.  Results do not depend on the layout.
-Layout mix_layout(int D, int L_low, int L_high) {
-  Layout lay = choose_layout(D, L_low, L_high);
-  if (lay.K == 16) {
-    lay.K = 8;
-    lay.lpc = (lay.npairs + 7) / 8;
-    lay.cpw = kWave / lay.lpc;
-  }
-  return lay;
-}
 
 hipError_t launch_mix_init(const MixArgs& m, const Layout& lay, bool replay, hipStream_t s) {
   return launch(m, lay, 0, replay, s);

@@ -21,7 +21,6 @@ struct MixArgs {
   double* row_E;         // [n] (energy)
 };
 
-Layout mix_layout(int D, int L_low, int L_high);   // choose_layout with at most 8 pairs per lane
 hipError_t launch_mix_init(const MixArgs& m, const Layout& lay, bool replay, hipStream_t s);
 hipError_t launch_mix_iters(const MixArgs& m, const Layout& lay, bool replay, hipStream_t s);
 hipError_t launch_mix_rows(const MixArgs& m, const Layout& lay, bool leapfrog, hipStream_t s);

@@ -18,9 +18,11 @@
 // sampled states are bit-identical to the NumPy reference on replayed streams.
 #include "hmc_debug.hpp"
 #include "hmc_device.hpp"
+#include "hmc_dispatch.hpp"
 #include "hmc_internal.hpp"
 #include "hmc_lane_group.hpp"
 #include "hmc_random_iter.hpp"
+#include "hmc_route.hpp"
 #include "hmc_target_ops.hpp"
 
 namespace hmc {
@@ -226,175 +228,33 @@ __global__ __launch_bounds__(256) void k_random_iters(RandArgs a) {
   tally.flush(a, ln.lane, (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave));
 }
 
-template <int K>
-hipError_t launch_init_k(const RandArgs& a, bool gen, bool replay, dim3 grid, hipStream_t s) {
-  if (gen) {
-    if (replay) k_random_init<K, true, true><<<grid, 256, 0, s>>>(a);
-    else k_random_init<K, true, false><<<grid, 256, 0, s>>>(a);
-  } else {
-    if (replay) k_random_init<K, false, true><<<grid, 256, 0, s>>>(a);
-    else k_random_init<K, false, false><<<grid, 256, 0, s>>>(a);
-  }
-  return hipGetLastError();
-}
-
-template <int K, bool EXACT>
-hipError_t launch_iters_k2(const RandArgs& a, bool gen, bool replay, dim3 grid, hipStream_t s) {
-  if (gen) {
-    if (replay) k_random_iters<K, EXACT, true, true><<<grid, 256, 0, s>>>(a);
-    else k_random_iters<K, EXACT, true, false><<<grid, 256, 0, s>>>(a);
-  } else {
-    if (replay) k_random_iters<K, EXACT, false, true><<<grid, 256, 0, s>>>(a);
-    else k_random_iters<K, EXACT, false, false><<<grid, 256, 0, s>>>(a);
-  }
-  return hipGetLastError();
-}
-
-template <int K>
-hipError_t launch_iters_k(const RandArgs& a, bool exact, bool gen, bool replay, dim3 grid, hipStream_t s) {
-  return exact ? launch_iters_k2<K, true>(a, gen, replay, grid, s)
-               : launch_iters_k2<K, false>(a, gen, replay, grid, s);
-}
-
 }  // namespace
 
-// E[max of c iid U{lo..hi-1}] — the wave runs as long as its longest trajectory.
-static double expected_max(int lo, int hi, int c) {
-  const int n = hi - lo;
-  if (n <= 1 || c <= 1) return 0.5 * (lo + hi - 1);
-  double e = 0.0, prev = 0.0;
-  for (int x = lo; x < hi; ++x) {
-    const double F = pow((double)(x - lo + 1) / n, c);
-    e += x * (F - prev);
-    prev = F;
-  }
-  return e;
+hipError_t launch_random_init(const RandArgs& a, const RandomRoute& r, bool replay, hipStream_t s) {
+  return with_value<1, 2, 4, 5, 8, 16>(r.lay.K, [&](auto K) {
+    return with_bool(r.gen, [&](auto GEN) {
+      return with_bool(replay, [&](auto REPLAY) {
+        k_random_init<K(), GEN(), REPLAY()><<<grid_for(a), 256, 0, s>>>(a);
+        return hipGetLastError();
+      });
+    });
+  });
 }
 
-Layout choose_layout(int D, int L_low, int L_high) {
-  static const int Ks[] = {1, 2, 4, 5, 8, 16};
-  Layout best{0, 0, 0, (D + 1) / 2};
-  if (const int K = force_K()) {   // debug build only: force the pairs-per-lane template
-    const int lpc = (best.npairs + K - 1) / K;
-    for (int k : Ks)
-      if (k == K && lpc <= kWave) return Layout{K, lpc, kWave / lpc, best.npairs};
-  }
-  // D > 64: one wavefront per chain (hmc_wave.hip): no trajectory-length divergence inside a
-  // wave, wave-uniform control flow; K pairs per lane.
-  if (best.npairs > kWave / 2) {
-    for (int K : {1, 2, 4, 8, 16})
-      if (K * kWave >= best.npairs) return Layout{K, kWave, 1, best.npairs};
-    return best;  // K = 0: unsupported
-  }
-  // small D: several chains per wave (lane groups); pick K by lane utilisation discounted by the
-  // expected trajectory-length divergence between the chains sharing a wave
-  double best_score = -1.0;
-  const double mean = 0.5 * (L_low + L_high - 1);
-  for (int K : Ks) {
-    const int lpc = (best.npairs + K - 1) / K;
-    if (lpc > kWave) continue;
-    const int cpw = kWave / lpc;
-    const double util = (double)best.npairs * cpw / (kWave * (double)K);
-    const double emax = expected_max(L_low, L_high, cpw);
-    const double score = util * (emax > 0 ? mean / emax : 1.0);
-    if (score > best_score + 1e-9) {
-      best_score = score;
-      best.K = K;
-      best.lpc = lpc;
-      best.cpw = cpw;
-    }
-  }
-  return best;
-}
-
-hipError_t launch_random_init(const RandArgs& a, const Layout& lay, bool gen, bool replay, hipStream_t s) {
-  const dim3 grid = grid_for(a);
-  switch (lay.K) {
-    case 1: return launch_init_k<1>(a, gen, replay, grid, s);
-    case 2: return launch_init_k<2>(a, gen, replay, grid, s);
-    case 4: return launch_init_k<4>(a, gen, replay, grid, s);
-    case 5: return launch_init_k<5>(a, gen, replay, grid, s);
-    case 8: return launch_init_k<8>(a, gen, replay, grid, s);
-    case 16: return launch_init_k<16>(a, gen, replay, grid, s);
-  }
-  return hipErrorInvalidValue;
-}
-
-// The wave-per-chain kernels (hmc_wave.hip) serve this layout.
-bool wave_layout(const Layout& lay) {
-  return lay.cpw == 1 && !force_group() && (lay.K == 1 || lay.K == 2 || lay.K == 4 || lay.K == 8 || lay.K == 16);
-}
-
-// Three-term leapfrog u[n+1] = (2 - (dt w)^2) u[n] - u[n-1] (hmc_wave.hip, TT): the momentum comes
-// back as a difference of the last two points divided by dt, whose rounding error grows like
-// eps |u| / (dt w).  Lower bound: the smallest dt w at which the NumPy model of the kernel's
-// operation order keeps E within 1e-12 relative of a long-double integration over 19 steps at
-// D = 100 (tests/leapfrog_model.py energy_deviation; DESIGN.md 3.1: below 1e-12 from 4.6e-4 up,
-// the bound is set a factor 2 above that); upper bound: the integrator's stability limit
-// dt w = 2.
-// Trajectory length: the rounded coefficient c = fl(2 - (dt w)^2) turns the phase by
-// (c - c_exact) / (2 sin theta) per step (cos theta = c / 2, sin theta = dt w sqrt(1 - (dt w)^2 / 4)),
-// and the orbit's amplitude is |p| / sqrt(1 - (dt w)^2 / 4), so after L steps q is off by about
-// |p| L |c - c_exact| / (2 dt w (1 - (dt w)^2 / 4)), with |c - c_exact| <= 2^-53 below (dt w)^2 = 2
-// and <= 2^-52 from there on ((dt w)^2 is rounded in [2, 4)).  The same model (max |q - q_ld| over
-// the trajectory at D = 100) stays below 2.2 x 2^-53 x L m / (dt w (1 - (dt w)^2 / 4)),
-// m = 1 or 2; the bound keeps that below 5e-11, half of the 1e-10 the routing test allows
-// (tests/test_leapfrog_form.py), i.e. a twentieth of FAST mode's 1e-9 on q.
-// Outside the range the two-FMA loop runs.
-// -DHMC_NO_THREE_TERM builds the library that never picks it (A/B).
-bool leapfrog_three_term(const RandArgs& a, const Layout& lay, bool exact, bool gen) {
-#ifdef HMC_NO_THREE_TERM
-  return false;
-#else
-  constexpr double kThreeTermMinDtw = 1e-3;
-  constexpr double kThreeTermMaxDrift = 2e5;   // L_high m / (dt w (1 - (dt w)^2 / 4)) at most
-  if (exact || gen || !wave_layout(lay)) return false;
-  const double dtw = a.dt < 0 ? -a.dt : a.dt;   // identity precision and mass: w = 1
-  const double dtw2 = dtw * dtw;
-  if (!(dtw2 >= kThreeTermMinDtw * kThreeTermMinDtw && dtw2 < 4.0)) return false;
-  const double m = dtw2 >= 2.0 ? 2.0 : 1.0;
-  return (double)a.L_high * m <= kThreeTermMaxDrift * dtw * (1.0 - 0.25 * dtw2);
-#endif
-}
-
-bool full_variant(const RandArgs& a) { return a.traj_q != nullptr || instrumented(a); }
-
-// Four chains per wavefront, one 16-lane row each (hmc_rows.hip): the shapes it is built for.  The
-// kernel packs L in 24 bits for its tallies and takes no empty trajectory.
-// -DHMC_NO_ROWS builds the library that never picks it (A/B).
-bool rows_shape(int D, int L_low, int L_high) {
-#ifdef HMC_NO_ROWS
-  return false;
-#else
-  return D >= 97 && D <= 112 && L_low >= 1 && L_high <= (1 << 12);
-#endif
-}
-
-// ... and the launches it takes: those of the production wave instance (FAST, identity target and
-// mass, three-term leapfrog, Philox, no chain-0 capture or debug hooks), with a sample window whose
-// rows of the wave's four chains lie within a 32-bit byte offset of the first, and so do their rows
-// of the energy chains.
-bool rows_kernel(const RandArgs& a, const Layout& lay, bool exact, bool gen, bool replay) {
-  if (replay || full_variant(a) || !rows_shape(a.D, a.L_low, a.L_high) || !leapfrog_three_term(a, lay, exact, gen)) return false;
-  if ((a.Ec || a.dEc) && 4 * (int64_t)a.Lc * 8 >= (int64_t)1 << 31) return false;
-  return !a.qc || 4 * (int64_t)a.Lq * a.D * 8 < (int64_t)1 << 31;
-}
-
-hipError_t launch_random_iters(const RandArgs& a, const Layout& lay, bool exact, bool gen, bool replay,
-                               hipStream_t s) {
-  if (rows_kernel(a, lay, exact, gen, replay)) return launch_rows_iters(a, s);
-  if (wave_layout(lay))
-    return launch_wave_iters(a, lay.K, exact, gen, replay, leapfrog_three_term(a, lay, exact, gen), s);
-  const dim3 grid = grid_for(a);
-  switch (lay.K) {
-    case 1: return launch_iters_k<1>(a, exact, gen, replay, grid, s);
-    case 2: return launch_iters_k<2>(a, exact, gen, replay, grid, s);
-    case 4: return launch_iters_k<4>(a, exact, gen, replay, grid, s);
-    case 5: return launch_iters_k<5>(a, exact, gen, replay, grid, s);
-    case 8: return launch_iters_k<8>(a, exact, gen, replay, grid, s);
-    case 16: return launch_iters_k<16>(a, exact, gen, replay, grid, s);
-  }
-  return hipErrorInvalidValue;
+hipError_t launch_random_iters(const RandArgs& a, const RandomRoute& r, bool exact, bool replay, hipStream_t s) {
+  if (r.kernel == RandomKernel::Rows) return launch_rows_iters(a, s);
+  if (r.kernel == RandomKernel::Wave) return launch_wave_iters(a, r.lay.K, exact, r.gen, replay, r.three_term, r.full, s);
+  if (r.kernel != RandomKernel::Groups) return hipErrorInvalidValue;
+  return with_value<1, 2, 4, 5, 8, 16>(r.lay.K, [&](auto K) {
+    return with_bool(exact, [&](auto EXACT) {
+      return with_bool(r.gen, [&](auto GEN) {
+        return with_bool(replay, [&](auto REPLAY) {
+          k_random_iters<K(), EXACT(), GEN(), REPLAY()><<<grid_for(a), 256, 0, s>>>(a);
+          return hipGetLastError();
+        });
+      });
+    });
+  });
 }
 
 }  // namespace hmc

@@ -16,6 +16,7 @@
 // HBM traffic per chain-iteration: one q_chain row (8D B) + E + dE (16 B).
 #include "hmc_debug.hpp"
 #include "hmc_device.hpp"
+#include "hmc_dispatch.hpp"
 #include "hmc_internal.hpp"
 #include "hmc_target_ops.hpp"
 
@@ -146,11 +147,11 @@ constexpr int kRingPairs = 128;
 // in the release library a FULL instance is the capture instance and nothing else.  The production
 // variant (FULL = false) drops both: their pointers and flags are live across the iteration loop
 // and pushed the SGPR demand past the 8-waves/SIMD budget (spills to VGPR lanes cost one
-// v_readlane/v_writelane VALU slot each, ~45 per iteration).  The host picks with full_variant.
+// v_readlane/v_writelane VALU slot each, ~45 per iteration).  The host picks (hmc_route.hpp, full).
 // ODD: D is odd (the ring zeroes the missing coordinate of the last pair); a template parameter so
 // that the common even-D kernel carries no per-pass test.
 // TT: the FAST identity-target leapfrog in its three-term (Störmer) form, one FMA per coordinate
-// per step (the host picks it where the momentum recovery is safe: leapfrog_three_term, hmc_random.hip).
+// per step (the host picks it where the momentum recovery is safe: hmc_route.cpp, leapfrog_three_term).
 template <int K, bool EXACT, bool GEN, bool REPLAY, bool FULL, bool ODD = false, bool TT = false>
 __device__ __forceinline__ void wave_iters(const RandArgs& a) {
   static_assert(!TT || (!EXACT && !GEN), "the three-term leapfrog serves the FAST identity-target kernels only");
@@ -643,67 +644,44 @@ __global__ __launch_bounds__(kK1Block) __attribute__((amdgpu_waves_per_eu(8))) v
 }
 
 template <int K, bool EXACT, bool GEN, bool REPLAY, bool TT>
-void launch_wave_one(const RandArgs& a, dim3 grid, hipStream_t s) {
-  const bool full = full_variant(a);
-  if constexpr (K == 1) {
-    const dim3 g1((unsigned)((a.n + kK1Block / kWave - 1) / (kK1Block / kWave)));
-    const bool odd = (a.D & 1) != 0 && !REPLAY;   // only the ring (Philox) path specialises on odd D
-    if (full) {
-      if (odd) k_wave_iters_k1<EXACT, GEN, REPLAY, true, !REPLAY, TT><<<g1, kK1Block, 0, s>>>(a);
-      else k_wave_iters_k1<EXACT, GEN, REPLAY, true, false, TT><<<g1, kK1Block, 0, s>>>(a);
+hipError_t launch_wave_one(const RandArgs& a, bool full, hipStream_t s) {
+  return with_bool(full, [&](auto FULL) {
+    if constexpr (K == 1) {
+      const dim3 grid((unsigned)((a.n + kK1Block / kWave - 1) / (kK1Block / kWave)));
+      // only the ring (Philox) path specialises on odd D
+      return with_bool((a.D & 1) != 0 && !REPLAY, [&](auto ODD) {
+        if constexpr (!(ODD() && REPLAY))
+          k_wave_iters_k1<EXACT, GEN, REPLAY, FULL(), ODD(), TT><<<grid, kK1Block, 0, s>>>(a);
+        return hipGetLastError();
+      });
     } else {
-      if (odd) k_wave_iters_k1<EXACT, GEN, REPLAY, false, !REPLAY, TT><<<g1, kK1Block, 0, s>>>(a);
-      else k_wave_iters_k1<EXACT, GEN, REPLAY, false, false, TT><<<g1, kK1Block, 0, s>>>(a);
+      k_wave_iters<K, EXACT, GEN, REPLAY, FULL(), TT><<<dim3((unsigned)((a.n + 3) / 4)), 256, 0, s>>>(a);
+      return hipGetLastError();
     }
-  } else {
-    if (full) k_wave_iters<K, EXACT, GEN, REPLAY, true, TT><<<grid, 256, 0, s>>>(a);
-    else k_wave_iters<K, EXACT, GEN, REPLAY, false, TT><<<grid, 256, 0, s>>>(a);
-  }
-}
-
-// tt (three-term leapfrog) only exists for the FAST identity-target instances
-template <int K, bool EXACT>
-hipError_t launch_wave_k2(const RandArgs& a, bool gen, bool replay, bool tt, dim3 grid, hipStream_t s) {
-  if (gen) {
-    if (replay) launch_wave_one<K, EXACT, true, true, false>(a, grid, s);
-    else launch_wave_one<K, EXACT, true, false, false>(a, grid, s);
-  } else if (!EXACT && tt) {
-    if (replay) launch_wave_one<K, EXACT, false, true, !EXACT>(a, grid, s);
-    else launch_wave_one<K, EXACT, false, false, !EXACT>(a, grid, s);
-  } else {
-    if (replay) launch_wave_one<K, EXACT, false, true, false>(a, grid, s);
-    else launch_wave_one<K, EXACT, false, false, false>(a, grid, s);
-  }
-  return hipGetLastError();
-}
-
-template <int K>
-hipError_t launch_wave_k(const RandArgs& a, bool exact, bool gen, bool replay, bool tt, dim3 grid, hipStream_t s) {
-  return exact ? launch_wave_k2<K, true>(a, gen, replay, tt, grid, s)
-               : launch_wave_k2<K, false>(a, gen, replay, tt, grid, s);
+  });
 }
 
 }  // namespace
 
-hipError_t launch_wave_iters(const RandArgs& a, int K, bool exact, bool gen, bool replay, bool three_term,
+hipError_t launch_wave_iters(const RandArgs& a, int K, bool exact, bool gen, bool replay, bool three_term, bool full,
                              hipStream_t s) {
 #ifdef HMC_WAVE_PROD_ONLY   // dev: ISA inspection of the headline instance only (seconds to compile)
-  if (K == 1 && !exact && !gen && !replay) {
-    if (three_term) launch_wave_one<1, false, false, false, true>(a, dim3(1), s);
-    else launch_wave_one<1, false, false, false, false>(a, dim3(1), s);
-    return hipGetLastError();
-  }
-  return hipErrorInvalidValue;
+  if (K != 1 || exact || gen || replay) return hipErrorInvalidValue;
+  return with_bool(three_term, [&](auto TT) { return launch_wave_one<1, false, false, false, TT()>(a, full, s); });
 #else
-  const dim3 grid((unsigned)((a.n + 3) / 4));
-  switch (K) {
-    case 1: return launch_wave_k<1>(a, exact, gen, replay, three_term, grid, s);
-    case 2: return launch_wave_k<2>(a, exact, gen, replay, three_term, grid, s);
-    case 4: return launch_wave_k<4>(a, exact, gen, replay, three_term, grid, s);
-    case 8: return launch_wave_k<8>(a, exact, gen, replay, three_term, grid, s);
-    case 16: return launch_wave_k<16>(a, exact, gen, replay, three_term, grid, s);
-  }
-  return hipErrorInvalidValue;
+  return with_value<1, 2, 4, 8, 16>(K, [&](auto K_) {
+    return with_bool(exact, [&](auto EXACT) {
+      return with_bool(gen, [&](auto GEN) {
+        return with_bool(replay, [&](auto REPLAY) {
+          // the three-term leapfrog only exists for the FAST identity-target instances
+          return with_bool(three_term && !exact && !gen, [&](auto TT) {
+            if constexpr (TT() && (EXACT() || GEN())) return hipErrorInvalidValue;
+            else return launch_wave_one<K_(), EXACT(), GEN(), REPLAY(), TT()>(a, full, s);
+          });
+        });
+      });
+    });
+  });
 #endif
 }
 

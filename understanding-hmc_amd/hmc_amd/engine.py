@@ -72,8 +72,9 @@ class RandomEngine:
 
     @staticmethod
     def _large_d(kind, D):
-        """hmc::big_path (csrc/hmc_big.hip): dense D > 128 (no MFMA tile layout), diagonal D > 2048
-        (more than 16 coordinate pairs per lane of a wave)."""
+        """The route's large-D rule (csrc/hmc_route.cpp big_path, RandomKernel::Big), restated: dense
+        D > 128 (no MFMA tile layout), diagonal D > 2048 (more than 16 coordinate pairs per lane of
+        a wave)."""
         return D > 128 if kind == H.HMC_TARGET_DENSE else (D + 1) // 2 > 16 * 64
 
     def _alloc_workspace(self, kind, order_tiles, random_ws):
